@@ -10,7 +10,14 @@ outer block, EDT, seeds, hmap, flood, size filter + regrow, halo crop +
 labelVolumeWithBackground, uint64 output with the block id offset.  `value` counts inner
 (output) voxels; inputs are resident in HBM when the timed region starts and the uint64
 outputs are written to HBM.  The PCIe-inclusive rate (host numpy input -> host numpy uint64
-output through ctws_ws_blocks) is reported beside it as `host_resident`.
+output through ctws_ws_blocks) is reported beside it as `host_resident` (with `--full`).
+
+A plain run (`--gpus 1 --steps N --warmup W`) stages the input, warms up, times the N steps and
+prints the result line; `--dump-outputs DIR` also writes what the last timed step computed
+(dump_outputs) to DIR/<name>.npy.  Everything else this file measures (the CPU baseline and the
+VI against it, the single-stream stage pass behind `roofline`, the config-5, host-resident,
+strong-scaling, end-to-end and thresholded-components legs) runs only with `--full`; their
+fields are null in a plain run's line.
 
 `--config N` runs the other BASELINE configs on one GPU (config 2: 512^3 3-D; config 4: 1024^3
 with halo [8,32,32]; config 5: one z-slab share of the 2048^3 uint8 two-pass run).
@@ -22,11 +29,11 @@ torchrun launch when WORLD_SIZE is set.  Weak scaling (`value`): every rank proc
 z-slab volume of the config; after each step the per-block label counts are all-gathered over
 RCCL and exclusively scanned into compact global id offsets (the exchange of
 relabel/find_labeling.py:104-116).  value = inner voxels of all ranks / max-over-ranks time.
-`strong_config4` (every run): config 4's whole 1024^3 volume cut into N z-slabs of the block grid
+`strong_config4` (every `--full` run): config 4's whole 1024^3 volume cut into N z-slabs of the block grid
 (BASELINE.json configs[3]: "blocks sharded over 8 MI355X, RCCL label-offset scan").
 Ranks that share a GPU (a rehearsal on a 1-GPU box) use a gloo group instead of RCCL.
 
-The CPU baseline (rank 0, N = 1) is the oracle (oracle/, the C++ restatement of the
+The CPU baseline (`--full`, rank 0, N = 1) is the oracle (oracle/, the C++ restatement of the
 reference path) on a bounded sample of the same workload, driven like LocalTask: one
 single-threaded process per block, n_jobs = min(n_blocks, cores).  It runs before any GPU
 initialisation so that no process is forked from a GPU process.  Worker 0's oracle output
@@ -498,13 +505,51 @@ def launch_check():
     dist.destroy_process_group()
 
 
+DUMP_SAMPLE_VALUES = 1 << 22   # label samples of all blocks of all ranks together (float64: 32 MB)
+DUMP_SEED = 20240
+
+
+def dump_outputs(dump_dir, rank, world, order, res, offsets, dev):
+    """--dump-outputs: what the last timed step handed to its caller, as float64 .npy files.
+
+    labels_sample: per block (the order the step ran them in) the uint64 labels of its output
+    tensor at a fixed set of positions, drawn once per block from a generator seeded with
+    DUMP_SEED + block id (the whole output when it has no more voxels than the block's share of
+    DUMP_SAMPLE_VALUES); block_results: (block id, status, max_label, n_ids) per block;
+    id_offsets: the compact global id offsets of the step's scan and, last, the id count."""
+    import torch
+    os.makedirs(dump_dir, exist_ok=True)
+    tag = '' if world == 1 else '_rank%d' % rank
+    per = max(1, DUMP_SAMPLE_VALUES // max(1, world * len(order)))   # (every rank writes its files)
+    samples = []
+    for b in order:
+        flat = b['output'].reshape(-1)
+        if flat.numel() > per:
+            g = torch.Generator().manual_seed(DUMP_SEED + int(b['block_id']))
+            idx = torch.randint(0, flat.numel(), (per,), generator=g).to(dev)
+            flat = flat[idx]
+        samples.append(flat.cpu().numpy().view(np.uint64).astype(np.float64))
+    n = max(len(s) for s in samples) if samples else 0
+    lab = np.zeros((len(samples), n), dtype=np.float64)
+    for i, s in enumerate(samples):
+        lab[i, :len(s)] = s
+    np.save(os.path.join(dump_dir, 'labels_sample%s.npy' % tag), lab)
+    np.save(os.path.join(dump_dir, 'block_results%s.npy' % tag),
+            np.array([[b['block_id']] + list(r) for b, r in zip(order, res)], dtype=np.float64).reshape(-1, 4))
+    if 'scan' in offsets:
+        np.save(os.path.join(dump_dir, 'id_offsets%s.npy' % tag),
+                np.concatenate([offsets['scan'], [offsets['n_ids']]]).astype(np.float64))
+
+
 def run_workload(cfg_id, scaling, rank, world, dev, steps, warmup, nstreams_req, host_pass=False,
-                 keep_block=None, keep_volume=False):
+                 keep_block=None, keep_volume=False, stage_pass=True, dump_dir=None):
     """Stage one workload in HBM, run `warmup` + timed `steps` steps, and measure it.
 
     A step = the `_ws_block` (and `_ws_pass2`) of every block of the rank's share, then the RCCL
     offset scan.  Returns the timing, the per-stage HIP-event times of one extra single-stream
-    step, the algorithmic bytes, and (host_pass, rank 0) the PCIe-inclusive rate."""
+    step (stage_pass; without it, and with more than one stream, stage_1 is None), the
+    algorithmic bytes, and (host_pass, rank 0) the PCIe-inclusive rate.  dump_dir: write the
+    outputs of the last timed step there (dump_outputs)."""
     import torch
     from cluster_tools_amd import ctws
     from cluster_tools_amd.synthetic import boundary_map_torch, ellipsoid_mask_torch
@@ -644,8 +689,9 @@ def run_workload(cfg_id, scaling, rank, world, dev, steps, warmup, nstreams_req,
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last = None
     for k in range(steps):
-        step(True)
+        last = step(True)
         progress('config %d step %d' % (cfg_id, k))
     torch.cuda.synchronize()
     if world > 1:
@@ -654,15 +700,20 @@ def run_workload(cfg_id, scaling, rank, world, dev, steps, warmup, nstreams_req,
     dt = sharded.all_reduce_max(dt_rank, device=dev)
     ms_ranks = [round(t / steps * 1e3, 3) for t in sharded.all_gather_float(dt_rank, device=dev)]
     stage_ms = {k: v / steps for k, v in stage_ms.items()}
+    if dump_dir:
+        dump_outputs(dump_dir, rank, world, [b for _, g, _ in groups for b in g], last, offsets, dev)
+        progress('config %d outputs of the last step written to %s' % (cfg_id, dump_dir))
     # roofline durations: one more, untimed step with every block on ONE stream, so that no
     # other stream's kernels share the chip while a launch runs (with concurrent streams the
     # HIP-event duration of a launch includes the time it shares)
     stage_1 = {}
-    if nstreams > 1:
+    if nstreams == 1:
+        stage_1 = stage_ms
+    elif stage_pass:
         step(True, ns=1, into=stage_1)
         torch.cuda.synchronize()
     else:
-        stage_1 = stage_ms
+        stage_1 = None
     inner_all = sharded.all_reduce_sum_int(inner_vox, device=dev)
 
     host = None
@@ -722,6 +773,12 @@ def roofline_of(cfg, m):
     """Per-stage GB/s, the dominant stage's roofline and the pipeline roofline of a measurement."""
     def per_stage(sm):
         return {k: sum(sm.get(p, 0.0) for p in STAGE_PARTS.get(k, (k,))) for k in stage_bytes(cfg)}
+    ms_per_step = m['dt'] / m['steps'] * 1e3
+    alg_total = alg_bytes(cfg, m['outer_vox'], m['inner_vox'], m['pass2_outer'])
+    pipe = alg_total / (ms_per_step * 1e-3) / 1e9
+    if m['stage_1'] is None:
+        # no single-stream stage times (a plain run on several streams): the pipeline figures only
+        return dict(dom=None, stage_gbs=None, alg_total=alg_total, pipe=pipe, ms_per_step=ms_per_step)
     sbytes = stage_bytes(cfg)
     stages = per_stage(m['stage_1'])
     stage_gbs = {}
@@ -735,19 +792,24 @@ def roofline_of(cfg, m):
     b_unit, unit = sbytes[dom]
     dom_bytes = b_unit * (m['outer_vox'] if unit == 'outer' else m['inner_vox'])
     achieved = dom_bytes / (dom_ms * 1e-3) / 1e9
-    ms_per_step = m['dt'] / m['steps'] * 1e3
-    alg_total = alg_bytes(cfg, m['outer_vox'], m['inner_vox'], m['pass2_outer'])
-    pipe = alg_total / (ms_per_step * 1e-3) / 1e9
     return dict(dom=dom, dom_ms=dom_ms, dom_bytes=dom_bytes, b_unit=b_unit, unit=unit, achieved=achieved,
                 stage_gbs=stage_gbs, alg_total=alg_total, pipe=pipe, ms_per_step=ms_per_step)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--config', type=int, default=DEFAULT_CONFIG, choices=sorted(CONFIGS))
+    ap.add_argument('--full', action='store_true',
+                    help='also run the side legs: the CPU baseline and the VI against it, the single-stream '
+                         'stage pass (roofline), config 5, the host-resident pass, strong scaling, the '
+                         'end-to-end workflow and the thresholded-components block; the --no-* options '
+                         'below take single legs out again')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (seeded label samples of every block, the '
+                         'per-block results, the id offsets) to DIR/<name>.npy as float64')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-host', action='store_true', help='skip the host-resident (PCIe-inclusive) pass')
     ap.add_argument('--no-e2e', action='store_true', help='skip the end-to-end n5 workflow run')
@@ -768,8 +830,18 @@ def main():
                          'the blocks are split between them so their launch-bound phases overlap')
     ap.add_argument('--launch-check', action='store_true',
                     help='start the ranks and their process group only (no GPU): a launcher test')
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    if not args.full:
+        # a plain run: set up, warm up, time the steps, print the line
+        args.no_cpu_baseline = args.no_host = args.no_e2e = args.no_strong = True
+        args.no_threshcc = args.no_config5 = True
+    return args
 
+
+def main():
+    args = parse_args()
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         # no launcher around us: start the ranks ourselves (nothing here has touched a GPU)
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -804,7 +876,8 @@ def main():
     devices = sorted(set(int(x) for x in (sharded_gather_devices(dev_index, dev) if world > 1 else [dev_index])))
 
     m = run_workload(args.config, args.scaling, rank, world, dev, args.steps, args.warmup, args.streams,
-                     host_pass=False, keep_block=ref_block[0] if ref_block else None)
+                     host_pass=False, keep_block=ref_block[0] if ref_block else None, stage_pass=args.full,
+                     dump_dir=args.dump_outputs)
     rf = roofline_of(cfg, m)
     value = m['inner_all'] * args.steps / m['dt'] / 1e9
 
@@ -891,9 +964,20 @@ def main():
 
     traffic = None
     pmc = os.path.join(HERE, 'profiles', 'pmc_traffic_c%d.json' % args.config)
-    if os.path.exists(pmc):
+    if os.path.exists(pmc) and rf['dom'] is not None:
         with open(pmc) as f:
             traffic = json.load(f).get(rf['dom'])
+
+    roofline = None
+    if rf['dom'] is not None:
+        roofline = {'bound': 'hbm', 'kernel': '%s (%s)' % (rf['dom'], STAGE_KERNELS[rf['dom']]),
+                    'ms_per_step': round(rf['dom_ms'], 3), 'achieved': round(rf['achieved'], 1),
+                    'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': round(rf['achieved'] / HBM_PEAK_GBS, 4),
+                    'traffic': traffic, 'alg_bytes': rf['dom_bytes'], 'alg_bytes_per_voxel': rf['b_unit'],
+                    'voxels': rf['unit'],
+                    'timing': 'HIP events on the library stream, one untimed step with all blocks on 1 stream',
+                    'traffic_unit': 'HBM bytes per step of the stage (profiles/pmc_traffic_c%d.json)'
+                                    % args.config}
 
     if rank == 0:
         line = {
@@ -914,14 +998,7 @@ def main():
                        'pass2_order': ('dependency levels of the sequential loop (watershed.pass2_levels, as '
                                        'the workflow): %d launch groups' % (m['ngroups'] - 1)) if two_pass else None},
             'ms_per_step_ranks': m['ms_ranks'],
-            'roofline': {'bound': 'hbm', 'kernel': '%s (%s)' % (rf['dom'], STAGE_KERNELS[rf['dom']]),
-                         'ms_per_step': round(rf['dom_ms'], 3), 'achieved': round(rf['achieved'], 1),
-                         'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': round(rf['achieved'] / HBM_PEAK_GBS, 4),
-                         'traffic': traffic, 'alg_bytes': rf['dom_bytes'], 'alg_bytes_per_voxel': rf['b_unit'],
-                         'voxels': rf['unit'],
-                         'timing': 'HIP events on the library stream, one untimed step with all blocks on 1 stream',
-                         'traffic_unit': 'HBM bytes per step of the stage (profiles/pmc_traffic_c%d.json)'
-                                         % args.config},
+            'full': args.full, 'roofline': roofline,
             'pipeline_roofline': {'alg_bytes_per_inner_voxel': round(rf['alg_total'] / m['inner_vox'], 1),
                                   'achieved': round(rf['pipe'], 1), 'unit': 'GB/s',
                                   'frac': round(rf['pipe'] / HBM_PEAK_GBS, 4)},
@@ -932,7 +1009,7 @@ def main():
             'thresholded_components': tcc,
             'vi_vs_oracle': vi,
             'stage_ms': {k: round(v, 3) for k, v in m['stage_ms'].items()},
-            'stage_ms_1stream': {k: round(v, 3) for k, v in m['stage_1'].items()},
+            'stage_ms_1stream': None if m['stage_1'] is None else {k: round(v, 3) for k, v in m['stage_1'].items()},
             'stage_gbs': rf['stage_gbs'],
             'global_ids': m['n_ids'],
             'cpu_baseline': cpu,

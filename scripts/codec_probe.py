@@ -1,7 +1,7 @@
 """zlib vs libdeflate (cluster_tools_amd/io/deflate.py) on a synthetic float32 boundary chunk and a
 uint64 label chunk: compression ratio, compress and inflate MB/s per thread."""
-import sys, time, zlib, ctypes as C, numpy as np
-sys.path.insert(0, '/root/repo')
+import os, sys, time, zlib, ctypes as C, numpy as np
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from cluster_tools_amd.synthetic import boundary_map
 L = C.CDLL('libdeflate.so.0')
 L.libdeflate_alloc_decompressor.restype = C.c_void_p
