@@ -1519,6 +1519,7 @@ int run_batch(ctws_handle* h, const ctws_cfg* cfg, const Plan& pl, ctws_block* b
     // ---- size filter + regrow ---------------------------------------------------------------
     std::vector<uint32_t> surv(TS, 1u);
     int n_auto_blocks = 0;
+    int n_sf_sparse = 0, n_sf_redo = 0;  // blocks whose removed segments were walked / walked, then scanned
     bool regrow_bad = false;  // the regrow's fixpoint check failed: the batch's blocks fail
     if (cfg->size_filter > 0) {
         uint32_t* counts = (uint32_t*)w.A;
@@ -1546,7 +1547,10 @@ int run_batch(ctws_handle* h, const ctws_cfg* cfg, const Plan& pl, ctws_block* b
             std::vector<BlockStat> s3(nb);
             // a small size filter: the removed segments walked from their seeds (k_sf_plan decides
             // per block; CTWS_SF_SPARSE=0 scans every block).  WatershedFromSeeds numbers its
-            // labels by seed value, without first positions: it scans
+            // labels by seed value, without first positions: it scans.  A pass-2 label is every
+            // voxel that carried one initial id, in several pieces where the outer block or a 2-D
+            // slice cut a pass-1 segment: a walk that reaches fewer voxels than its label counts
+            // hands its block back to the scan below (BlockStat::sf_redo)
             const bool sparse_ok = h->sf_sparse && !pl.from_seeds && cfg->size_filter <= 64;
             const uint32_t* rootpos = pl.pass2 ? (const uint32_t*)w.dt : (const uint32_t*)w.Bf;
             auto regrow_init = [&]() -> int {
@@ -1577,6 +1581,8 @@ int run_batch(ctws_handle* h, const ctws_cfg* cfg, const Plan& pl, ctws_block* b
                 bool need = false;
                 for (int z = 0; z < ns; ++z) need |= !surv[desc[i].sbase + z];
                 n_auto_blocks += need;
+                n_sf_sparse += sparse_ok && s3[i].sf_sparse;
+                n_sf_redo += sparse_ok && s3[i].sf_redo;
             }
             if (n_auto_blocks) {
                 // every segment of a slice / block removed: vigra seeds the regrow from the strict
@@ -1775,6 +1781,8 @@ int run_batch(ctws_handle* h, const ctws_cfg* cfg, const Plan& pl, ctws_block* b
     add_timing(h, "flood_fallback", (float)fallback);
     add_timing(h, "regrow_rounds", (float)rounds2);
     add_timing(h, "auto_seeded_blocks", (float)n_auto_blocks);
+    add_timing(h, "sf_sparse_blocks", (float)n_sf_sparse);
+    add_timing(h, "sf_redo_blocks", (float)n_sf_redo);
     add_timing(h, "flood_kernel_ms", fk1);
     add_timing(h, "flood_packed", packed ? 1.f : 0.f);
     add_timing(h, "flood_tiles_solved", (float)h->flood_tiles);

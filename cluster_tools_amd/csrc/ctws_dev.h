@@ -63,7 +63,7 @@ struct BlockStat {
     uint32_t dsat;            // packed flood: a key's hop distance d reached kDMax (note_dsat)
     uint32_t _u;              // 2-D seeds: plateau maxima listed by k_seed_members<2>
     uint32_t sf_sparse;       // size filter: the removed segments are walked, not scanned (k_sf_plan)
-    uint32_t _q;
+    uint32_t sf_redo;         // a walked label was in several pieces (pass 2): the block is scanned (k_sf_sparse)
 };
 
 // BlockStat::err bits (a failed block does not fail its batch; the caller sees the status)

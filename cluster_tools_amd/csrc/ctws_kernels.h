@@ -232,7 +232,7 @@ __global__ void k_hist2d(const BlockDesc*, const BlockStat*, const uint32_t*, co
                          uint32_t*, int);
 __global__ void k_sf_plan(const BlockDesc*, BlockStat*, uint32_t, const uint32_t*, const uint8_t*, const uint32_t*,
                           uint32_t*);
-__global__ void k_sf_sparse(const BlockDesc*, const BlockStat*, uint32_t, const uint32_t*, const uint8_t*,
+__global__ void k_sf_sparse(const BlockDesc*, BlockStat*, uint32_t, const uint32_t*, const uint8_t*,
                             const uint32_t*, const float*, uint64_t*, uint8_t*, uint64_t*, uint64_t*);
 __global__ void k_fixed_from_open(const BlockDesc*, const BlockStat*, const uint64_t*, uint8_t*);
 template <int U>

@@ -177,6 +177,9 @@ __global__ void __launch_bounds__(256) k_hist2d(const BlockDesc* __restrict__ D,
 // sparse blocks.  The walk writes what k_regrow_init would write where the regrow reads it: the
 // removed voxels' keys (INF), seed flags and open bits, and the surviving neighbours' changed bits
 // and seed keys (h, 0, label) -- survivors elsewhere are never read by the regrow.
+// Pass 2: a label is every voxel that carried one initial id, and a pass-1 segment cut by the
+// outer block or by a 2-D slice is in several pieces, of which the walk reaches one.  The walk
+// counts what it claims, and a block with a label it did not exhaust is scanned after all.
 constexpr uint32_t kSfSparseMax = 64;  // the largest size filter walked (a segment below it fits the queue)
 
 // a label survives the size filter: count >= size_filter, or (pass 2) an excluded initial id
@@ -218,22 +221,25 @@ __global__ void __launch_bounds__(256) k_sf_plan(const BlockDesc* __restrict__ D
     const uint32_t unreached = (uint32_t)B.N - tot;
     const bool sparse = size_filter <= kSfSparseMax && !unreached && !bare &&
                         (uint64_t)nsmall * size_filter <= (uint64_t)B.N / 8;
-    if (threadIdx.x == 0) st.sf_sparse = sparse ? 1u : 0u;
+    if (threadIdx.x == 0) {
+        st.sf_sparse = sparse ? 1u : 0u;
+        st.sf_redo = 0u;
+    }
     if (sparse)
         for (int z = threadIdx.x; z < (B.nd_ws == 2 ? B.Z : 1); z += 256) survivors[B.sbase + z] = 1u;
 }
 
 // one thread per label of the block: a removed segment (count < size_filter) is walked from its
 // seed (breadth first, in-plane 4-neighbourhood in 2-D ws mode, 6 in 3-D)
-__global__ void __launch_bounds__(256) k_sf_sparse(const BlockDesc* __restrict__ D, const BlockStat* S,
+__global__ void __launch_bounds__(256) k_sf_sparse(const BlockDesc* __restrict__ D, BlockStat* S,
                                                    uint32_t size_filter, const uint32_t* __restrict__ counts,
                                                    const uint8_t* __restrict__ excl,
                                                    const uint32_t* __restrict__ rootpos, const float* __restrict__ h,
                                                    uint64_t* __restrict__ key, uint8_t* __restrict__ fixedv,
                                                    uint64_t* __restrict__ open, uint64_t* __restrict__ chg) {
     const BlockDesc& B = D[blockIdx.y];
-    const BlockStat& st = S[blockIdx.y];
-    if (!st.active || !st.sf_sparse) return;
+    BlockStat& st = S[blockIdx.y];
+    if (!st.active || !st.sf_sparse) return;  // (a block handed back to the scan: nothing more to walk)
     const uint32_t l = 1u + blockIdx.x * blockDim.x + threadIdx.x;
     if (l > st.n_seeds) return;
     const uint32_t* c = counts + B.base;
@@ -289,6 +295,15 @@ __global__ void __launch_bounds__(256) k_sf_sparse(const BlockDesc* __restrict__
                 fixedv[B.base + u] = 1;
             }
         }
+    }
+    // the walk reached fewer voxels than the label has: the label is in several pieces, and the
+    // others still hold their keys.  The block goes back to k_regrow_init, which runs after this
+    // kernel and writes every voxel and every bitmap word of the block from the keys and the
+    // counts alone; what the walks of the block wrote (removed voxels' keys INF, survivors' seed
+    // keys) is what the scan writes there too, so it starts from any mixture of both.
+    if ((uint32_t)qt != c[l]) {
+        st.sf_sparse = 0u;
+        st.sf_redo = 1u;
     }
 }
 

@@ -103,3 +103,29 @@ def make_cases():
         '3d_no_sizefilter': (dict(D3, size_filter=0), dict(input=x)),
         '3d_sigma0_alpha1': (dict(D3, sigma_seeds=0, alpha=1.0), dict(input=x)),
     }
+
+
+def mixed_regrow_blocks():
+    """Two pass-1 blocks for one size_filter 25 call: a regular boundary map, whose few small
+    segments k_sf_plan has walked (k_sf_sparse), and uniform noise, whose small segments exceed
+    N / (8 * 25), so k_regrow_init scans it.  Both kinds share the batch's regrow bitmaps."""
+    return [dict(input=boundary_map((16, 64, 80), seed=21), block_id=1),
+            dict(input=np.random.RandomState(22).rand(12, 48, 80).astype(np.float32), block_id=2)]
+
+
+def mixed_regrow_plans(config, blocks):
+    """k_sf_plan's conditions per block, from the oracle's unfiltered result: -> [(sparse, nsmall)]"""
+    from oracle import oracle as O
+    sf = config['size_filter']
+    with O.flood_model():
+        raw = O.ws_blocks(dict(config, size_filter=0), BLOCK_SHAPE, blocks)
+    plans = []
+    for r in raw:
+        o = r['output']  # (2-D: the slices' offsets keep the ids of different slices apart)
+        assert r['status'] == 0
+        c = np.unique(o, return_counts=True)[1]
+        nsmall = int((c < sf).sum())
+        planes = list(o) if config.get('apply_ws_2d', True) else [o]
+        kept = all((np.unique(p, return_counts=True)[1] >= sf).any() for p in planes)
+        plans.append((nsmall * sf <= o.size // 8 and kept and not (o == 0).any(), nsmall))
+    return plans

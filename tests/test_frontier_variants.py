@@ -14,6 +14,7 @@ import pytest
 
 from oracle import oracle as O
 from cases import make_cases, BLOCK_SHAPE
+from pass2_cases import SPLIT_CASES
 
 pytestmark = pytest.mark.gpu
 
@@ -81,12 +82,19 @@ def test_variant_matches_model(variant_handle, name):
 _REF2 = {}
 
 
-@pytest.mark.parametrize('name', ['2d', '3d', '3d_mask', '2d_collide'])
+@pytest.mark.parametrize('name', ['2d', '3d', '3d_mask', '2d_collide',
+                                  'split_2d', 'split_3d', 'edges_2d', 'edges_3d', 'big64_3d'])
 def test_variant_pass2_matches_model(variant_handle, name):
     """_ws_pass2 under every knob: pass 2's size filter keeps the excluded initial ids whatever
-    their size, on the sparse walk (first positions of the relabelled ids) and on the scan."""
-    from pass2_cases import scenario
-    config, block_shape, blocks = scenario(name)
+    their size and removes the others when small, every piece of them (the split cases of
+    pass2_cases.py, compared on the whole outer block), on the sparse walk (first positions of
+    the relabelled ids, redone by the scan where a walk missed a piece) and on the scan."""
+    from pass2_cases import scenario, split_case, split_model
+    if name in SPLIT_CASES:
+        config, block_shape, blocks, _ = split_case(name)
+        _REF2[name] = split_model(name)
+    else:
+        config, block_shape, blocks = scenario(name)
     if name not in _REF2:
         with O.flood_model():
             _REF2[name] = O.ws_blocks(config, block_shape, blocks, pass_id=1)

@@ -12,7 +12,7 @@ import pytest
 
 from cluster_tools_amd.metrics import vi_scores, rand_scores
 from oracle import oracle as O
-from cases import make_cases, BLOCK_SHAPE
+from cases import make_cases, mixed_regrow_blocks, mixed_regrow_plans, BLOCK_SHAPE
 
 pytestmark = pytest.mark.gpu
 
@@ -157,6 +157,27 @@ def test_batch_of_mixed_blocks_equals_single_blocks(gpu_handle):
         ref = O.ws_blocks(cfg, BLOCK_SHAPE, [b])[0]
         vis, vim = vi_scores(t['output'], ref['output'])
         assert vis + vim <= VI_TOL
+
+
+@pytest.mark.parametrize('mode', ['2d', '3d'])
+def test_mixed_regrow_plans_in_one_batch(gpu_handle, mode):
+    config = dict({} if mode == '2d' else dict(apply_dt_2d=False, apply_ws_2d=False), sigma_seeds=1.0, size_filter=25)
+    blocks = mixed_regrow_blocks()
+    (sparse_a, nsmall_a), (sparse_b, _) = mixed_regrow_plans(config, blocks)
+    assert sparse_a and nsmall_a > 0 and not sparse_b
+    with O.flood_model():
+        ref = O.ws_blocks(config, BLOCK_SHAPE, blocks)
+    single = [gpu_handle.ws_blocks(config, BLOCK_SHAPE, [b])[0] for b in blocks]
+    for order in ((0, 1), (1, 0)):
+        together = gpu_handle.ws_blocks(config, BLOCK_SHAPE, [blocks[i] for i in order])
+        tm = gpu_handle.timings()
+        # one batch, one block of it walked, none handed back to the scan
+        assert (tm['host_batches'], tm['sf_sparse_blocks'], tm['sf_redo_blocks']) == (1, 1, 0), tm
+        for i, t in zip(order, together):
+            assert t['status'] == ref[i]['status'] == 0
+            np.testing.assert_array_equal(t['output'], single[i]['output'])
+            np.testing.assert_array_equal(t['output'], ref[i]['output'])
+            assert t['max_label'] == single[i]['max_label'] == ref[i]['max_label']
 
 
 def test_device_path_matches_host_path(gpu_handle):

@@ -10,7 +10,8 @@ import pytest
 
 from cluster_tools_amd.metrics import vi_scores, rand_scores
 from oracle import oracle as O
-from pass2_cases import SCENARIOS, scenario
+from pass2_cases import (SCENARIOS, SPLIT_CASES, SF_SPARSE_MAX, SPLIT_ID_BASE, assert_split_preconditions, scenario, split_case, split_model,
+                         whole_outer)
 
 pytestmark = pytest.mark.gpu
 
@@ -47,6 +48,79 @@ def test_pass2_fragments_vi(gpu_handle, name):
         halo_ids = set(np.unique(init[init != 0] & np.uint64(0xFFFFFFFF)).tolist())
         assert halo_ids & set(np.unique(g['output']).tolist()) or not halo_ids
         assert g['output'].shape == init[sl].shape
+
+
+@pytest.mark.parametrize('name', sorted(SCENARIOS))
+def test_pass2_whole_outer_matches_model(gpu_handle, name):
+    """The inner block set to the outer block: what pass 2 computes in its halo (the size
+    filter's removals there move the 2-D slice offsets and the regrow of the inner block)."""
+    config, block_shape, blocks = scenario(name)
+    blocks = [whole_outer(b) for b in blocks]
+    with O.flood_model():
+        ref = O.ws_blocks(config, block_shape, blocks, pass_id=1)
+    res = gpu_handle.ws_blocks(config, block_shape, blocks, pass_id=1)
+    for b, r, g in zip(blocks, ref, res):
+        assert g['status'] == r['status']
+        assert g['output'].shape == b['input'].shape
+        np.testing.assert_array_equal(g['output'], r['output'])
+        assert g['max_label'] == r['max_label']
+
+
+@pytest.mark.parametrize('name', sorted(SPLIT_CASES))
+def test_pass2_split_ids_match_model(gpu_handle, name):
+    """Initial ids in several pieces, each id below the size filter and not excluded: the
+    reference's apply_size_filter removes every piece (pass2_cases.py), whichever piece holds
+    the id's first position."""
+    assert_split_preconditions(name)
+    config, block_shape, blocks, _ = split_case(name)
+    res = gpu_handle.ws_blocks(config, block_shape, blocks, pass_id=1)
+    t = gpu_handle.timings()
+    for r, g in zip(split_model(name), res):
+        assert g['status'] == r['status'] == 0
+        np.testing.assert_array_equal(g['output'], r['output'])
+        assert g['max_label'] == r['max_label']
+    # the path under test: every block was planned sparse, and its walks met a label in pieces
+    # (a size filter above kSfSparseMax: no walk at all)
+    assert t['sf_sparse_blocks'] == 0, t
+    assert t['sf_redo_blocks'] == (len(blocks) if config['size_filter'] <= SF_SPARSE_MAX else 0), t
+
+
+def test_pass2_split_block_beside_a_walked_block(gpu_handle):
+    """One batch, in both orders: a block whose walks meet split ids (handed back to the scan)
+    and a block whose labels are all connected (walked), sharing the regrow bitmaps."""
+    config, block_shape, (split,), _ = split_case('edges_3d')
+    plain = whole_outer(scenario('3d', id_base=SPLIT_ID_BASE)[2][1])
+    with O.flood_model():
+        ref = [split_model('edges_3d')[0], O.ws_blocks(config, block_shape, [plain], pass_id=1)[0]]
+    blocks = [split, plain]
+    for order in ((0, 1), (1, 0)):
+        res = gpu_handle.ws_blocks(config, block_shape, [blocks[i] for i in order], pass_id=1)
+        t = gpu_handle.timings()
+        assert (t['host_batches'], t['sf_sparse_blocks'], t['sf_redo_blocks']) == (1, 1, 1), t
+        for i, g in zip(order, res):
+            assert g['status'] == ref[i]['status'] == 0
+            np.testing.assert_array_equal(g['output'], ref[i]['output'])
+            assert g['max_label'] == ref[i]['max_label']
+
+
+@pytest.mark.parametrize('name', sorted(SPLIT_CASES))
+def test_pass2_split_ids_device_path(gpu_handle, name):
+    import torch
+    config, block_shape, blocks, _ = split_case(name)
+    host = gpu_handle.ws_blocks(config, block_shape, blocks, pass_id=1)
+    dev = []
+    for b in blocks:
+        d = dict(input=torch.from_numpy(b['input']).cuda(), block_id=b['block_id'], inner_begin=b['inner_begin'],
+                 initial_seeds=torch.from_numpy(b['initial_seeds'].view(np.int64)).cuda(),
+                 output=torch.zeros(tuple(b['inner_shape']), dtype=torch.int64, device='cuda'))
+        if b.get('mask') is not None:
+            d['mask'] = torch.from_numpy(np.ascontiguousarray(b['mask'], dtype=np.uint8)).cuda()
+        dev.append(d)
+    st = gpu_handle.ws_blocks_device(config, block_shape, dev, pass_id=1)
+    for h, d, s in zip(host, dev, st):
+        assert s[0] == h['status'] == 0
+        assert s[1] == h['max_label']
+        assert np.array_equal(d['output'].cpu().numpy().view(np.uint64), h['output'])
 
 
 def test_pass2_empty_block_writes_nothing(gpu_handle):
