@@ -159,6 +159,9 @@ struct ctws_handle {
     int host_batch_blocks = 0;  // CTWS_HOST_BATCH_BLOCKS: cap on blocks per host-path batch (0: voxel cap)
     int64_t host_batch_voxels = (int64_t)256 << 20;  // CTWS_HOST_BATCH_VOXELS: smaller batches pipeline better
     int edt_wz = 0;  // CTWS_EDT_WZ: the same for the z pass alone (3-D DT)
+    // CTWS_EDT_BITS=0: the x pass writes g2 per voxel for every batch (k_prep_edt_x_co / _reg and
+    // k_edt_col) instead of the records of k_edt_col_bits
+    int edt_bits = 1;
     int edt_w = 0;  // CTWS_EDT_W (8, 16, 32, 64): x positions per EDT column tile (0: by line length)
     // CTWS_FRONTIER_CHUNK2D / _3D "CWxCYxCZ": frontier chunk brick (words x rows x slices, 64 words).
     // 3-D batches with a mask: 1x32x2 was their default until round 5 (a masked region is one
@@ -1083,6 +1086,10 @@ int run_batch(ctws_handle* h, const ctws_cfg* cfg, const Plan& pl, ctws_block* b
     mark("start");
 
     // ---- normalize + threshold + EDT ------------------------------------------------------
+    // typed batches on the integer EDT hand the rows' foreground bits to the y pass (one EdtRec
+    // per word, in w.key: free until the seeds are labelled) instead of g2 per voxel in w.A
+    bool edt_bits = false;
+    EdtRec* const edt_rec = (EdtRec*)w.key;
     {
         // one raw dtype and 3-D datasets in the batch: the typed kernels (global loads in flight)
         int dt = desc[0].dtype;
@@ -1092,6 +1099,7 @@ int run_batch(ctws_handle* h, const ctws_cfg* cfg, const Plan& pl, ctws_block* b
             typed &= d.dtype == dt && d.n_channels == 0;
             all_exact &= d.X == maxX && (d.X == 256 || d.X == 512 || d.X == 1024) && d.n_channels == 0 && d.dtype == 3;
         }
+        edt_bits = h->edt_bits && typed && !real_edt && !pl.from_seeds && 2 * TF <= T;
         dim3 g((unsigned)std::min<int64_t>((maxN + 65535) / 65536, 256), nb);
         if (typed) {
             dim3 gm((unsigned)std::min<int64_t>((maxN + 8 * 256 - 1) / (8 * 256), 1024), nb);
@@ -1111,25 +1119,33 @@ int run_batch(ctws_handle* h, const ctws_cfg* cfg, const Plan& pl, ctws_block* b
         // rows up to 1024 voxels: one wave per row in registers.  f32 rows of exactly 64 K voxels
         // move as float4 with lanes owning consecutive voxels (k_prep_edt_x_reg); other rows use
         // the lane-interleaved coalesced layout (k_prep_edt_x_co)
-        auto launch_co = [&](auto kmax_c) {
+        auto launch_co = [&](auto kmax_c, auto bits_c) {
             constexpr int KM = decltype(kmax_c)::value;
-            if (dt == CTWS_U8) k_prep_edt_x_co<KM, uint8_t><<<gx, 256, 0, h->stream>>>(w.desc, w.stat, pp, fin_out, (uint32_t*)w.A);
-            else if (dt == CTWS_U16) k_prep_edt_x_co<KM, uint16_t><<<gx, 256, 0, h->stream>>>(w.desc, w.stat, pp, fin_out, (uint32_t*)w.A);
-            else if (dt == CTWS_F32) k_prep_edt_x_co<KM, float><<<gx, 256, 0, h->stream>>>(w.desc, w.stat, pp, fin_out, (uint32_t*)w.A);
-            else k_prep_edt_x_co<KM, double><<<gx, 256, 0, h->stream>>>(w.desc, w.stat, pp, fin_out, (uint32_t*)w.A);
+            constexpr bool BITS = decltype(bits_c)::value;
+            auto go = [&](auto kern) { kern<<<gx, 256, 0, h->stream>>>(w.desc, w.stat, pp, fin_out, (uint32_t*)w.A, edt_rec); };
+            if (dt == CTWS_U8) go(k_prep_edt_x_co<KM, uint8_t, BITS>);
+            else if (dt == CTWS_U16) go(k_prep_edt_x_co<KM, uint16_t, BITS>);
+            else if (dt == CTWS_F32) go(k_prep_edt_x_co<KM, float, BITS>);
+            else go(k_prep_edt_x_co<KM, double, BITS>);
         };
-        if (typed && all_exact && maxX == 256)
+        if (edt_bits && maxX <= 256)
+            launch_co(std::integral_constant<int, 4>(), std::true_type());
+        else if (edt_bits && maxX <= 512)
+            launch_co(std::integral_constant<int, 8>(), std::true_type());
+        else if (edt_bits)
+            launch_co(std::integral_constant<int, 16>(), std::true_type());
+        else if (typed && all_exact && maxX == 256)
             k_prep_edt_x_reg<4><<<gx, 256, 0, h->stream>>>(w.desc, w.stat, pp, fin_out, (uint32_t*)w.A);
         else if (typed && all_exact && maxX == 512)
             k_prep_edt_x_reg<8><<<gx, 256, 0, h->stream>>>(w.desc, w.stat, pp, fin_out, (uint32_t*)w.A);
         else if (typed && all_exact && maxX == 1024)
             k_prep_edt_x_reg<16><<<gx, 256, 0, h->stream>>>(w.desc, w.stat, pp, fin_out, (uint32_t*)w.A);
         else if (typed && maxX <= 256)
-            launch_co(std::integral_constant<int, 4>());
+            launch_co(std::integral_constant<int, 4>(), std::false_type());
         else if (typed && maxX <= 512)
-            launch_co(std::integral_constant<int, 8>());
+            launch_co(std::integral_constant<int, 8>(), std::false_type());
         else if (typed && maxX <= 1024)
-            launch_co(std::integral_constant<int, 16>());
+            launch_co(std::integral_constant<int, 16>(), std::false_type());
         else {
             lds_optin(k_prep_edt_x, 4 * (size_t)maxX * 4);
             k_prep_edt_x<<<gx, 256, 4 * (size_t)maxX * 4, h->stream>>>(w.desc, w.stat, pp, fin_out, (uint32_t*)w.A);
@@ -1179,7 +1195,7 @@ int run_batch(ctws_handle* h, const ctws_cfg* cfg, const Plan& pl, ctws_block* b
             return W;
         };
         const int Wy = fit(h->edt_w ? h->edt_w : edt_col_width(maxY), maxY);
-        EdtColParams ep{1, pl.pitch[1] * pl.pitch[1], pl.dt_2d, pl.dt_2d, 0u};
+        EdtColParams ep{1, pl.pitch[1] * pl.pitch[1], pl.dt_2d, pl.dt_2d, 0u, pl.pitch[2] * pl.pitch[2]};
         dim3 gy((unsigned)((int64_t)maxZ * ((maxX + Wy - 1) / Wy)), nb);
         const size_t ldsy = (size_t)maxY * Wy * 4;
         // columns that may go to the lower-envelope pass: one entry each at most
@@ -1204,9 +1220,19 @@ int run_batch(ctws_handle* h, const ctws_cfg* cfg, const Plan& pl, ctws_block* b
             else if (W == 32) go(k_edt_col<32>);
             else if (W == 16) go(k_edt_col<16>);
             else go(k_edt_col<8>);
-            k_edt_col_fh<<<gfh, 256, 0, h->stream>>>(w.desc, w.stat, p, gin, gout, w.dt, w.smin, w.smax, fh_list, cnt);
+            k_edt_col_fh<<<gfh, 256, 0, h->stream>>>(w.desc, w.stat, p, gin, nullptr, gout, w.dt, w.smin, w.smax, fh_list, cnt);
         };
-        launch_col(Wy, gy, ldsy, ep, (uint32_t*)w.A, (uint32_t*)w.Bf, fh_cnt);
+        // the record-fed y pass: 16 columns through a ring of 256 rows (16 KiB of LDS whatever
+        // the column length; the other tile shapes measured are in DESIGN.md section 3)
+        auto launch_col_bits = [&](EdtColParams p, uint32_t* gout, uint32_t* cnt) {
+            constexpr int W = 16, RING = 256;
+            dim3 g((unsigned)((int64_t)maxZ * ((maxX + W - 1) / W)), nb);
+            k_edt_col_bits<W, RING><<<g, 256, (size_t)RING * W * 4, h->stream>>>(w.desc, w.stat, p, edt_rec, gout, w.dt,
+                                                                                 w.smin, w.smax, fh_list, cnt);
+            k_edt_col_fh<<<gfh, 256, 0, h->stream>>>(w.desc, w.stat, p, nullptr, edt_rec, gout, w.dt, w.smin, w.smax, fh_list, cnt);
+        };
+        if (edt_bits) launch_col_bits(ep, (uint32_t*)w.Bf, fh_cnt);
+        else launch_col(Wy, gy, ldsy, ep, (uint32_t*)w.A, (uint32_t*)w.Bf, fh_cnt);
         LAUNCHCHK();
         if (!pl.dt_2d) {
             const int Wz = fit(h->edt_wz ? h->edt_wz : h->edt_w ? h->edt_w : edt_col_width(maxZ), maxZ);
@@ -2412,6 +2438,7 @@ int ctws_open(int device, ctws_handle** out) {
     if (const char* t = std::getenv("CTWS_SF_SPARSE")) h->sf_sparse = std::atoi(t);
     if (const char* t = std::getenv("CTWS_VERIFY")) h->verify = std::atoi(t);
     if (const char* t = std::getenv("CTWS_PREP_LDS")) h->prep_lds = std::atoi(t);
+    if (const char* t = std::getenv("CTWS_EDT_BITS")) h->edt_bits = std::atoi(t);
     if (const char* t = std::getenv("CTWS_FRONTIER_ITERS"))
         h->frontier_max_iters = std::max(0, std::min(kFrontierMaxItersCap, std::atoi(t)));
     if (const char* t = std::getenv("CTWS_GAUSS_YX")) h->gauss_yx = std::atoi(t);

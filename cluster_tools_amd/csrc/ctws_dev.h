@@ -234,6 +234,33 @@ __device__ __forceinline__ bool bit_of(const uint64_t* bits, const BlockDesc& B,
     return (bits[B.fbase + (int64_t)row * ((B.X + 63) >> 6) + (x >> 6)] >> (x & 63)) & 1ull;
 }
 
+// ---- EDT x pass -> y pass handoff ------------------------------------------------------------
+// One record per (row, 64-voxel word), laid out as the frontier bitmaps' words are (fbase):
+// the word's foreground bits and the x of the nearest foreground voxel of the row before / after
+// the word.  The squared x distance of any voxel of the word follows without a scan of the row.
+struct __attribute__((aligned(16))) EdtRec {
+    uint64_t bits;  // foreground ballot of the word
+    int32_t prev;   // x of the last foreground voxel before the word, -1: none
+    int32_t next;   // x of the first foreground voxel after the word, 0x3FFFFFFF: none
+};
+// distance along x from voxel x (in word x >> 6, whose record is R) to the nearest foreground
+// voxel of its row; 0x3FFFFFFF on a row without foreground
+__device__ __forceinline__ int edt_xdist_of(const EdtRec& R, int x) {
+    const int b = x & 63, x0 = x & ~63;
+    const uint64_t ml = R.bits & (~0ull >> (63 - b));  // bits <= b
+    const uint64_t mr = R.bits & (~0ull << b);         // bits >= b
+    const int left = ml ? x0 + 63 - __builtin_clzll(ml) : R.prev;
+    const int right = mr ? x0 + __builtin_ctzll(mr) : R.next;
+    const int dl = left < 0 ? 0x3FFFFFFF : x - left;
+    const int dr = right >= 0x3FFFFFFF ? 0x3FFFFFFF : right - x;
+    return min(dl, dr);
+}
+// the x pass's g2 (k_prep_edt_x_co): px2 d^2, kInfD2 on a row without foreground
+__device__ __forceinline__ uint32_t edt_g2_of(const EdtRec& R, int x, int px2) {
+    const int d = edt_xdist_of(R, x);
+    return d >= 0x3FFFFFFF ? kInfD2 : (uint32_t)(px2 * d * d);
+}
+
 // label of a CC member from its parent slot p = P[i] after k_root_label (0: background)
 __device__ __forceinline__ uint32_t cc_label(const uint32_t* P, uint32_t p) {
     if (p == kNoParent) return 0u;

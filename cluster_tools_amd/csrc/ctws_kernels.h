@@ -17,6 +17,7 @@ struct EdtColParams {
     int final_pass;
     int per_slice;
     uint32_t max_dist;
+    int px2;  // x pitch squared: the record-fed y pass computes the x pass's g2 itself
 };
 struct EdtRealParams {
     double pitch[3];
@@ -43,8 +44,8 @@ __global__ void k_input_minmax(const BlockDesc*, BlockStat*);
 __global__ void k_prep_edt_x(const BlockDesc*, BlockStat*, PrepParams, float*, uint32_t*);
 template <int KMAX>
 __global__ void k_prep_edt_x_reg(const BlockDesc*, BlockStat*, PrepParams, float*, uint32_t*);
-template <int KMAX, class T>
-__global__ void k_prep_edt_x_co(const BlockDesc*, BlockStat*, PrepParams, float*, uint32_t*);
+template <int KMAX, class T, bool BITS>
+__global__ void k_prep_edt_x_co(const BlockDesc*, BlockStat*, PrepParams, float*, uint32_t*, EdtRec*);
 template <class T>
 __global__ void k_input_minmax_t(const BlockDesc*, BlockStat*);
 constexpr int kEdtSearchCap = 48;  // bounded-search steps before a column goes to k_edt_col_fh
@@ -52,8 +53,11 @@ template <int W>
 __global__ void k_edt_col(const BlockDesc*, BlockStat*, EdtColParams, const uint32_t*, uint32_t*, float*, uint32_t*,
                           uint32_t*, unsigned long long*, uint32_t*);
 __global__ void k_sqrt_int_check(uint32_t, uint32_t, float*);
-__global__ void k_edt_col_fh(const BlockDesc*, BlockStat*, EdtColParams, const uint32_t*, uint32_t*, float*, uint32_t*,
-                             uint32_t*, const unsigned long long*, const uint32_t*);
+template <int W, int RING>
+__global__ void k_edt_col_bits(const BlockDesc*, BlockStat*, EdtColParams, const EdtRec*, uint32_t*, float*, uint32_t*,
+                               uint32_t*, unsigned long long*, uint32_t*);
+__global__ void k_edt_col_fh(const BlockDesc*, BlockStat*, EdtColParams, const uint32_t*, const EdtRec*, uint32_t*,
+                             float*, uint32_t*, uint32_t*, const unsigned long long*, const uint32_t*);
 template <class T>
 __global__ void k_edt_real_init(const BlockDesc*, const BlockStat*, EdtRealParams, const uint32_t*, T*);
 template <class T>

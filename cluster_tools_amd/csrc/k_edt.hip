@@ -8,7 +8,9 @@
 //   pass y : min_y' g(y') + p_y^2 (y - y')^2, LDS-staged columns, bounded search
 //   pass z : same along z, then min(d2, ceil(dmax)) and sqrtf (correctly rounded)
 // HBM traffic per outer voxel: x-pass reads the input (4 B f32 / 1 B u8) and writes the
-// normalized input (4 B) and g^2 (4 B); y and z passes read 4 B and write 4 B each.
+// normalized input (4 B) and g^2 (4 B); y and z passes read 4 B and write 4 B each.  Typed
+// batches on the integer EDT (run_batch: edt_bits) hand the y pass the rows' foreground bits
+// instead: the x pass writes 0.25 B per voxel of records (EdtRec), which the y pass expands.
 #include "ctws_kernels.h"
 
 namespace ctws {
@@ -283,9 +285,14 @@ template __global__ void k_prep_edt_x_reg<16>(const BlockDesc*, BlockStat*, Prep
 // of x comes from mk[k] masked at the lane plus the last / first foreground of the segments
 // before / after.  3-D datasets only (4-D inputs use k_prep_edt_x).  Same results as
 // k_prep_edt_x.
-template <int KMAX, class T>
+// BITS: g2 is a pure function of the row's foreground bits, so instead of 4 B per voxel the
+// y pass gets one EdtRec per 64-voxel word (mk[k], lastk[k - 1], firstk[k + 1]: 0.25 B per
+// voxel) and computes g2 itself (edt_g2_of).  Records lie as the frontier bitmaps' words do:
+// rec[fbase + row * ceil(X / 64) + k].
+template <int KMAX, class T, bool BITS>
 __global__ void __launch_bounds__(256) k_prep_edt_x_co(const BlockDesc* __restrict__ D, BlockStat* S, PrepParams pp,
-                                                       float* __restrict__ fin, uint32_t* __restrict__ g2) {
+                                                       float* __restrict__ fin, uint32_t* __restrict__ g2,
+                                                       EdtRec* __restrict__ rec) {
     const BlockDesc& B = D[blockIdx.y];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + wave;
@@ -337,6 +344,19 @@ __global__ void __launch_bounds__(256) k_prep_edt_x_co(const BlockDesc* __restri
             firstk[k] = f;
         }
     }
+    if (BITS) {
+        // lane k hands over the record of word k
+        EdtRec r{0ull, -1, 0x3FFFFFFF};
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k)
+            if (lane == k) {
+                r.bits = mk[k];
+                r.prev = k > 0 ? lastk[k - 1] : -1;
+                r.next = k + 1 < KMAX ? firstk[k + 1] : 0x3FFFFFFF;
+            }
+        if (lane < K) rec[B.fbase + row * K + lane] = r;
+        return;
+    }
     const uint64_t le = (lane == 63) ? ~0ull : ((2ull << lane) - 1ull);  // bits <= lane
     const uint64_t ge = ~0ull << lane;                                    // bits >= lane
 #pragma unroll
@@ -351,15 +371,22 @@ __global__ void __launch_bounds__(256) k_prep_edt_x_co(const BlockDesc* __restri
         if (k < K && x < X) g2[B.base + rbase + x] = (d >= 0x3FFFFFFF) ? kInfD2 : (uint32_t)(pp.px2 * d * d);
     }
 }
-#define CTWS_PREP_CO(K)                                                                                \
-    template __global__ void k_prep_edt_x_co<K, uint8_t>(const BlockDesc*, BlockStat*, PrepParams, float*, uint32_t*);  \
-    template __global__ void k_prep_edt_x_co<K, uint16_t>(const BlockDesc*, BlockStat*, PrepParams, float*, uint32_t*); \
-    template __global__ void k_prep_edt_x_co<K, float>(const BlockDesc*, BlockStat*, PrepParams, float*, uint32_t*);    \
-    template __global__ void k_prep_edt_x_co<K, double>(const BlockDesc*, BlockStat*, PrepParams, float*, uint32_t*);
-CTWS_PREP_CO(4)
-CTWS_PREP_CO(8)
-CTWS_PREP_CO(16)
+#define CTWS_PREP_CO1(K, T, BITS)                                                                               \
+    template __global__ void k_prep_edt_x_co<K, T, BITS>(const BlockDesc*, BlockStat*, PrepParams, float*, uint32_t*, \
+                                                         EdtRec*);
+#define CTWS_PREP_CO(K, BITS)      \
+    CTWS_PREP_CO1(K, uint8_t, BITS)  \
+    CTWS_PREP_CO1(K, uint16_t, BITS) \
+    CTWS_PREP_CO1(K, float, BITS)    \
+    CTWS_PREP_CO1(K, double, BITS)
+CTWS_PREP_CO(4, false)
+CTWS_PREP_CO(8, false)
+CTWS_PREP_CO(16, false)
+CTWS_PREP_CO(4, true)
+CTWS_PREP_CO(8, true)
+CTWS_PREP_CO(16, true)
 #undef CTWS_PREP_CO
+#undef CTWS_PREP_CO1
 
 // per-block min / max of a 3-D input of type T: 8 global loads in flight per thread
 template <class T>
@@ -414,22 +441,24 @@ __device__ __forceinline__ float sqrt_rn_f(float x) {
     return r;
 }
 
-// correctly rounded sqrtf of an integer n < 2^24 without double arithmetic: v_sqrt_f32 (1 ulp)
-// gives r, the correctly rounded value is r - 1 ulp, r or r + 1 ulp, chosen by exact integer tests
-// of the midpoints.  r = R 2^-k (R the 24-bit significand): the upper midpoint is (2R + 1)
-// 2^-(k+1), below sqrt(n) iff (2R + 1)^2 < n 2^(2k+2); both sides are about 4 R^2 < 2^50.
+// correctly rounded sqrtf of an integer 0 <= n < 2^24 in float arithmetic alone: v_sqrt_f32 gives r
+// within 1 ulp, so the correctly rounded value is r - 1 ulp, r or r + 1 ulp, decided by the
+// midpoint tests on e = fma(-r, r, n).  With u = ulp(r) and r = R u (R the 24-bit significand),
+// n - r^2 = E u^2 for an integer |E| < 2^25, and the upper midpoint (R + 1/2) u is below sqrt(n)
+// iff E > R + 1/4, that is E >= R + 1.  The fma rounds E to 24 bits, which is monotone and keeps
+// the representable R and R + 1 apart, so the rounded e > r u (an exact product) decides it.
+// Likewise r is too high iff -E >= R (lower neighbour one u below), or -E >= R / 2 when r is a
+// power of two (lower neighbour u / 2 below).  Every n < 2^24 is checked against the correctly
+// rounded value by k_sqrt_int_check's test; the decision holds for any r within 1 ulp.
 __device__ __forceinline__ float sqrt_rn_int(uint32_t n) {
     if (n == 0u) return 0.0f;
-    const float r = __builtin_amdgcn_sqrtf((float)n);  // n < 2^24: exact conversion
+    const float x = (float)n;  // n < 2^24: exact conversion
+    const float r = __builtin_amdgcn_sqrtf(x);
     const uint32_t bits = __float_as_uint(r);
-    const uint64_t R = (uint64_t)((bits & 0x7FFFFFu) | 0x800000u);
-    const int k = 150 - (int)(bits >> 23);  // r = R 2^-k, 12 <= k <= 23 for 1 <= n < 2^24
-    const uint64_t n4 = (uint64_t)n << (2 * k + 2);
-    if ((2 * R + 1) * (2 * R + 1) < n4) return __uint_as_float(bits + 1u);
-    // lower midpoint: (2R - 1) 2^-(k+1), or (2^25 - 1) 2^-(k+2) when r is a power of two
-    const bool pow2 = R == 0x800000ull;
-    const uint64_t ml = pow2 ? (1ull << 25) - 1ull : 2 * R - 1;
-    if (ml * ml > (pow2 ? n4 << 2 : n4)) return __uint_as_float(bits - 1u);
+    const float e = __builtin_fmaf(-r, r, x);
+    const float ru = r * __uint_as_float((bits & 0x7F800000u) - (23u << 23));  // r ulp(r), exact
+    if (e > ru) return __uint_as_float(bits + 1u);
+    if (-e >= ((bits & 0x7FFFFFu) ? ru : 0.5f * ru)) return __uint_as_float(bits - 1u);
     return r;
 }
 
@@ -563,6 +592,145 @@ CTWS_EDT_COL(16)
 CTWS_EDT_COL(8)
 #undef CTWS_EDT_COL
 
+// ---- EDT pass along y from the x pass's records (EdtRec) ---------------------------------
+// k_edt_col with another staging phase: the tile's g2 is expanded into LDS from one 16-B record
+// per (row, word) instead of read as 4 B per voxel.  Tile: W consecutive x positions (W divides
+// 64: one record serves a tile row) x the column, walked in windows through a ring of RING rows
+// (a power of two; row p lives in slot p % RING).  The search of row p reads rows
+// p - kEdtSearchCap .. p + kEdtSearchCap at most, so with the rows of [y0 - HALO, y1 + HALO)
+// resident the window [y0, y1) searches as on the whole column; every row is staged once and
+// the LDS does not grow with Y.  The kernel is bound by its vector instructions, not by its
+// loads, so the search loop is kept short: the line is padded with kInfD2 rows
+// instead of clamped indices and selects, and p2 r^2 advances by its differences.  The values, the columns queued for
+// k_edt_col_fh, the final / non-final outputs and the statistics are k_edt_col's.
+template <int W, int RING>
+__global__ void __launch_bounds__(256) k_edt_col_bits(const BlockDesc* __restrict__ D, BlockStat* S, EdtColParams ep,
+                                                      const EdtRec* __restrict__ rec, uint32_t* __restrict__ gout,
+                                                      float* __restrict__ dt, uint32_t* __restrict__ slice_min,
+                                                      uint32_t* __restrict__ slice_max, unsigned long long* fh_list,
+                                                      uint32_t* fh_cnt) {
+    static_assert(64 % W == 0 && RING > 0 && (RING & (RING - 1)) == 0, "tile within one word, ring a power of two");
+    extern __shared__ __attribute__((aligned(16))) int smem_i[];
+    uint32_t* col = (uint32_t*)smem_i;
+    __shared__ unsigned long long capped_cols;  // bit c: a voxel of column c hit kEdtSearchCap
+    const BlockDesc& B = D[blockIdx.y];
+    if (!S[blockIdx.y].active) return;
+    const int nxc = (B.X + W - 1) / W;
+    const int L = B.Y;
+    const int t = blockIdx.x;
+    if (t >= B.Z * nxc) return;
+    const int o = t / nxc, xc = t % nxc;
+    const int xb = xc * W;
+    const int64_t lstride = B.X;
+    const int64_t obase = (int64_t)o * B.Y * B.X;
+    const int c = threadIdx.x % W;
+    const int r0 = threadIdx.x / W;
+    constexpr int RS = 256 / W;
+    constexpr int HALO = kEdtSearchCap + 1;
+    const bool colok = xb + c < B.X;
+    const int x = colok ? xb + c : B.X - 1;
+    const int wpr = (B.X + 63) >> 6;
+    const EdtRec* rsrc = rec + B.fbase + (int64_t)o * L * wpr + (x >> 6);
+    const int px2 = ep.px2;
+    auto g2at = [&](int q) -> uint32_t { return col[(q & (RING - 1)) * W + c]; };
+    if (threadIdx.x == 0) capped_cols = 0ull;
+    uint32_t mn = 0xFFFFFFFFu, mx = 0u;
+    const uint32_t maxd = ep.per_slice ? (uint32_t)(B.Y * B.Y + B.X * B.X) : B.maxd;
+    bool capped_any = false;
+    const uint32_t p2 = (uint32_t)ep.p2;
+    constexpr int RH = (RING - 2 * HALO) / RS * RS;  // rows per window
+    const int64_t cbase = B.base + obase + xb + c;
+    // Rows -HALO .. -1 and L .. L + HALO - 1 are staged as kInfD2, which is what the search takes
+    // for a candidate outside the line.  On lines longer than 2 kEdtSearchCap + 2 every row has
+    // candidates at all radii up to the cap on one side at least (rlim > kEdtSearchCap), so its
+    // search needs neither clamps nor selects.
+    const bool padded = L > 2 * kEdtSearchCap + 2;
+    for (int q = r0 - HALO; q < 0; q += RS) col[(q & (RING - 1)) * W + c] = kInfD2;
+    int staged = 0;
+    for (int y0 = 0; y0 < L; y0 += RH) {
+        const int y1 = min(L, y0 + RH);
+        const int need = y1 + HALO;  // rows beyond the line: no foreground
+        staged_loop<4>(
+            staged + r0, need, RS, [&](int p) { return p < L ? rsrc[(int64_t)p * wpr] : EdtRec{0ull, -1, 0x3FFFFFFF}; },
+            [&](int p, const EdtRec& R) { col[(p & (RING - 1)) * W + c] = colok ? edt_g2_of(R, x, px2) : kInfD2; });
+        staged = need;
+        __syncthreads();
+        int64_t gi = cbase + (int64_t)(y0 + r0) * lstride;  // voxel (p, xb + c) in the outer arrays
+        for (int p = y0 + r0; p < y1; p += RS, gi += RS * lstride) {
+            uint32_t best = g2at(p);
+            // radii r and r + 1 per step, as in k_edt_col
+            const int rlim = max(p, L - 1 - p);  // no candidates beyond
+            const int rcap = min(rlim, kEdtSearchCap);
+            int r = 1;
+            bool capped;
+            if (padded) {
+                // p2 r^2 by its differences (rr = p2 r^2, st = p2 (2 r + 1))
+                uint32_t rr = p2, st = 3u * p2;
+                int up = p - 1, dn = p + 1;
+                for (; r <= kEdtSearchCap; r += 2) {
+                    if (rr >= best) break;
+                    const uint32_t rr1 = rr + st;
+                    const uint32_t m0 = min(g2at(up), g2at(dn));
+                    const uint32_t m1 = min(g2at(up - 1), g2at(dn + 1));
+                    best = min(best, min(m0 + rr, m1 + rr1));
+                    rr = rr1 + st + 2u * p2;
+                    st += 4u * p2;
+                    up -= 2;
+                    dn += 2;
+                }
+                capped = rr < best;  // rr = p2 r^2; r <= rlim here
+            } else {
+                for (; r <= rcap; r += 2) {
+                    const uint32_t rr0 = p2 * (uint32_t)(r * r);
+                    if (rr0 >= best) break;
+                    const uint32_t rr1 = p2 * (uint32_t)((r + 1) * (r + 1));
+                    const uint32_t a = g2at(max(p - r, 0)), b = g2at(min(p + r, L - 1));
+                    const uint32_t a1 = g2at(max(p - r - 1, 0)), b1 = g2at(min(p + r + 1, L - 1));
+                    const uint32_t m0 = min(p - r >= 0 ? a : kInfD2, p + r < L ? b : kInfD2);
+                    const uint32_t m1 = min(p - r - 1 >= 0 ? a1 : kInfD2, p + r + 1 < L ? b1 : kInfD2);
+                    best = min(best, min(m0 + rr0, m1 + rr1));
+                }
+                capped = r <= rlim && p2 * (uint32_t)(r * r) < best;
+            }
+            if (!colok) continue;
+            capped_any |= capped;
+            if (ep.final_pass && capped) {
+                // k_edt_col_fh rewrites the column
+            } else if (ep.final_pass) {
+                const uint32_t d2 = min(best, maxd);
+                const float v = sqrt_rn_int(d2);
+                dt[gi] = v;
+                const uint32_t ov = ordf(v);
+                mn = min(mn, ov);
+                mx = max(mx, ov);
+            } else {
+                gout[gi] = best;
+            }
+        }
+        __syncthreads();  // the next window's rows replace the oldest
+    }
+    if (capped_any) atomicOr(&capped_cols, 1ull << c);
+    __syncthreads();
+    if (threadIdx.x < W && ((capped_cols >> threadIdx.x) & 1ull)) {
+        const uint32_t e = atomicAdd(fh_cnt, 1u);
+        fh_list[e] = ((unsigned long long)blockIdx.y << 48) | ((unsigned long long)o << 24) |
+                     (unsigned long long)(xb + threadIdx.x);
+    }
+    if (ep.final_pass) {
+        mn = wg_reduce_u32(mn, OpMin());
+        mx = wg_reduce_u32(mx, OpMax());
+        if (threadIdx.x == 0) {
+            atomic_min_if(&S[blockIdx.y].dt_min, mn);
+            atomic_max_if(&S[blockIdx.y].dt_max, mx);
+            atomic_min_if(&slice_min[B.sbase + o], mn);
+            atomic_max_if(&slice_max[B.sbase + o], mx);
+        }
+    }
+}
+
+template __global__ void k_edt_col_bits<16, 256>(const BlockDesc*, BlockStat*, EdtColParams, const EdtRec*, uint32_t*,
+                                                  float*, uint32_t*, uint32_t*, unsigned long long*, uint32_t*);
+
 // floor(a / b) for b > 0
 __device__ __forceinline__ int64_t floor_div(int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
 
@@ -573,9 +741,11 @@ __device__ __forceinline__ int64_t floor_div(int64_t a, int64_t b) { return a >=
 // stack (s | t << 16 per entry, t = first position of the entry's interval) lives in the
 // column's own output cells: entry k sits at position k <= t[k] <= u, so the backward pass
 // reads an entry before the output of its position is written.  Same values as the bounded
-// search (min over all finite g of g[s] + p2 (u - s)^2, kInfD2 on an all-INF line).
+// search (min over all finite g of g[s] + p2 (u - s)^2, kInfD2 on an all-INF line).  With `rec`
+// (y pass after the bits-writing x pass) the column's g comes from the records, not from gin.
 __global__ void __launch_bounds__(256) k_edt_col_fh(const BlockDesc* __restrict__ D, BlockStat* S, EdtColParams ep,
-                                                    const uint32_t* __restrict__ gin, uint32_t* gout, float* dt,
+                                                    const uint32_t* __restrict__ gin,
+                                                    const EdtRec* __restrict__ rec, uint32_t* gout, float* dt,
                                                     uint32_t* __restrict__ slice_min, uint32_t* __restrict__ slice_max,
                                                     const unsigned long long* __restrict__ fh_list,
                                                     const uint32_t* __restrict__ fh_cnt) {
@@ -588,13 +758,17 @@ __global__ void __launch_bounds__(256) k_edt_col_fh(const BlockDesc* __restrict_
         const int64_t lstride = (ep.axis == 1) ? B.X : (int64_t)B.Y * B.X;
         const int64_t obase = (ep.axis == 1) ? (int64_t)o * B.Y * B.X : (int64_t)o * B.X;
         const int64_t cb = B.base + obase + x;
-        const uint32_t* g = gin + cb;
+        const int wpr = (B.X + 63) >> 6;
+        const EdtRec* rcol = rec ? rec + B.fbase + (int64_t)o * B.Y * wpr + (x >> 6) : nullptr;
+        auto g = [&](int u) -> uint32_t {
+            return rcol ? edt_g2_of(rcol[(int64_t)u * wpr], x, ep.px2) : gin[cb + u * lstride];
+        };
         uint32_t* stk = (ep.final_pass ? (uint32_t*)dt : gout) + cb;
         const int64_t p2 = ep.p2;
         int q = -1, s_top = 0, t_top = 0;
         int64_t g_top = 0;
         for (int u = 0; u < L; ++u) {
-            const uint32_t gu32 = g[u * lstride];
+            const uint32_t gu32 = g(u);
             if (gu32 >= kInfD2) continue;
             const int64_t gu = gu32;
             while (q >= 0) {
@@ -605,7 +779,7 @@ __global__ void __launch_bounds__(256) k_edt_col_fh(const BlockDesc* __restrict_
                     const uint32_t wd = stk[q * lstride];
                     s_top = (int)(wd & 0xFFFFu);
                     t_top = (int)(wd >> 16);
-                    g_top = g[s_top * lstride];
+                    g_top = g(s_top);
                 }
             }
             if (q < 0) {
@@ -636,7 +810,7 @@ __global__ void __launch_bounds__(256) k_edt_col_fh(const BlockDesc* __restrict_
                     const uint32_t wd = stk[q * lstride];
                     s_top = (int)(wd & 0xFFFFu);
                     t_top = (int)(wd >> 16);
-                    g_top = g[s_top * lstride];
+                    g_top = g(s_top);
                 }
             }
             if (ep.final_pass) {
