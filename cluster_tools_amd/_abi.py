@@ -12,6 +12,8 @@ CTWS_OK = 0
 CTWS_U8, CTWS_U16, CTWS_F32, CTWS_F64 = 1, 2, 3, 4
 CTWS_AGG = {'mean': 0, 'max': 1, 'min': 2}
 CTWS_BLOCK_WRITTEN, CTWS_BLOCK_SKIPPED_MASK, CTWS_BLOCK_EMPTY, CTWS_BLOCK_EMPTY_PASS2, CTWS_BLOCK_FAILED = 0, 1, 2, 3, 4
+# ctws_size_filter_blocks: every label 0 (nothing written) / no discard id in the block (output = labels)
+CTWS_BLOCK_ZERO, CTWS_BLOCK_COPIED = 5, 6
 
 _DTYPE_CODES = {np.dtype('uint8'): CTWS_U8, np.dtype('uint16'): CTWS_U16,
                 np.dtype('float32'): CTWS_F32, np.dtype('float64'): CTWS_F64}

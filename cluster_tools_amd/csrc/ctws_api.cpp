@@ -122,6 +122,13 @@ struct ctws_handle {
     DevBuf edt_scratch;  // k_edt_real_line: per-thread parabola stacks
     // WatershedFromSeeds (k_seeded.hip): distinct seed values, sorted values, segment offsets, sort temp
     DevBuf fs_vals, fs_sorted, fs_off, fs_tmp;
+    // SizeFilterWorkflow (k_sizefilter.hip): the resident discard set (sorted ids; a bitmap over
+    // [ids[0], ids[n - 1]] when that range is small), the blocks' descriptors, facts and seeds
+    // (labels with the discarded ids zeroed), host-pointer staging of labels / height maps / outputs
+    DevBuf sf_ids, sf_bits, sf_desc, sf_stat, sf_seeds, sf_lab, sf_hm, sf_out;
+    int64_t sf_n = 0;
+    uint64_t sf_lo = 1, sf_hi = 0;
+    bool sf_has_bits = false;
     // ThresholdedComponents (k_threshcc.hip): forest, root bitmap, chunk counts / offsets, word
     // offsets, min / max + any flag, host-pointer staging
     DevBuf tc_P, tc_bits, tc_cnt, tc_offs, tc_woff, tc_red, tc_in, tc_mask, tc_out, tc_raw, tc_tmp, tc_taps;
@@ -356,6 +363,9 @@ struct Plan {
     // validated, derived configuration
     int nd_ws, dt_2d, pass2;
     int from_seeds;  // WatershedFromSeeds (watershed_from_seeds.py): given seeds, hmap = input
+    // the filling size filter (postprocess/filling_size_filter.py) on the from_seeds plan: the
+    // hmap is the RAW input cast to float32 (no normalize) and the seeds keep their uint64 values
+    int sf_fill;
     int pitch[3];
     double pitchd[3];  // pixel_pitch as given
     bool real_pitch;   // a non-integer pitch: vigra's double-temporary distance path
@@ -365,6 +375,7 @@ struct Plan {
 
 int make_plan(ctws_handle* h, const ctws_cfg* cfg, Plan& p) {
     p.from_seeds = 0;
+    p.sf_fill = 0;
     p.nd_ws = cfg->apply_ws_2d ? 2 : 3;
     p.dt_2d = cfg->apply_dt_2d ? 1 : 0;
     if (cfg->pass_id != 0 && cfg->pass_id != 1) {
@@ -790,28 +801,29 @@ void add_timing(ctws_handle* h, const char* name, float v) {
 // The blocks' distinct seed values (hash), sorted per block (segmented radix sort), a label
 // per value = 1 + its rank; blocks without any seed get the strict minima of the hmap
 // (k_auto_minima + the bitmap rank, labels written by k_fs_auto_label once `packed` is known).
+template <class V>
 int fs_seeds(ctws_handle* h, const std::vector<BlockDesc>& desc, int nb, int64_t TH, int64_t TW, int64_t TS,
-             int64_t maxH, int64_t maxRows, dim3 vg, dim3 wg) {
+             int64_t maxH, int64_t maxRows, dim3 vg, dim3 wg, V /* value type: uint32_t or uint64_t */) {
     Workspace& w = h->ws;
     int r;
     const size_t nh = (size_t)std::max<int64_t>(TH, 1);
-    if ((r = grow(h, h->fs_vals, sizeof(uint32_t) * nh)) != CTWS_OK) return r;
-    if ((r = grow(h, h->fs_sorted, sizeof(uint32_t) * nh)) != CTWS_OK) return r;
+    if ((r = grow(h, h->fs_vals, sizeof(V) * nh)) != CTWS_OK) return r;
+    if ((r = grow(h, h->fs_sorted, sizeof(V) * nh)) != CTWS_OK) return r;
     if ((r = grow(h, h->fs_off, sizeof(int) * 2 * (size_t)nb)) != CTWS_OK) return r;
-    uint32_t* vals = (uint32_t*)h->fs_vals.p;
-    uint32_t* sorted = (uint32_t*)h->fs_sorted.p;
+    V* vals = (V*)h->fs_vals.p;
+    V* sorted = (V*)h->fs_sorted.p;
     int* off = (int*)h->fs_off.p;
     HIPCHK(hipMemsetAsync(w.hkey, 0xFF, sizeof(uint64_t) * nh, h->stream));
-    k_fs_insert<<<vg, 256, 0, h->stream>>>(w.desc, w.stat, w.hkey);
+    k_fs_insert<V><<<vg, 256, 0, h->stream>>>(w.desc, w.stat, w.hkey);
     const dim3 hg((unsigned)std::min<int64_t>((maxH + 255) / 256, 4096), nb);
-    k_fs_collect<<<hg, 256, 0, h->stream>>>(w.desc, w.stat, w.hkey, vals);
+    k_fs_collect<V><<<hg, 256, 0, h->stream>>>(w.desc, w.stat, w.hkey, vals);
     k_fs_offsets<<<(nb + 255) / 256, 256, 0, h->stream>>>(w.desc, w.stat, nb, off, off + nb);
     LAUNCHCHK();
     size_t tb = 0;
     HIPCHK(fs_segmented_sort(nullptr, tb, vals, sorted, (int)nh, nb, off, off + nb, h->stream));
     if ((r = grow(h, h->fs_tmp, tb)) != CTWS_OK) return r;
     HIPCHK(fs_segmented_sort(h->fs_tmp.p, tb, vals, sorted, (int)nh, nb, off, off + nb, h->stream));
-    k_fs_rank<<<hg, 256, 0, h->stream>>>(w.desc, w.stat, w.hkey, sorted, w.hpos);
+    k_fs_rank<V><<<hg, 256, 0, h->stream>>>(w.desc, w.stat, w.hkey, sorted, w.hpos);
     LAUNCHCHK();
     std::vector<BlockStat> st(nb);
     HIPCHK(hipMemcpyAsync(st.data(), w.stat, sizeof(BlockStat) * nb, hipMemcpyDeviceToHost, h->stream));
@@ -1090,7 +1102,12 @@ int run_batch(ctws_handle* h, const ctws_cfg* cfg, const Plan& pl, ctws_block* b
     // per word, in w.key: free until the seeds are labelled) instead of g2 per voxel in w.A
     bool edt_bits = false;
     EdtRec* const edt_rec = (EdtRec*)w.key;
-    {
+    if (pl.sf_fill) {
+        // the height map as it is stored: no min / max, normalize or EDT pass
+        k_sf_hmap<<<vg, 256, 0, h->stream>>>(w.desc, w.hm);
+        k_fs_active<<<(nb + 255) / 256, 256, 0, h->stream>>>(w.desc, w.stat, nb);
+        LAUNCHCHK();
+    } else {
         // one raw dtype and 3-D datasets in the batch: the typed kernels (global loads in flight)
         int dt = desc[0].dtype;
         bool typed = !h->prep_lds && maxX <= 1024;
@@ -1161,7 +1178,10 @@ int run_batch(ctws_handle* h, const ctws_cfg* cfg, const Plan& pl, ctws_block* b
     std::vector<BlockStat> s2(nb);
     const dim3 gsb((unsigned)((maxZ + 255) / 256), nb);
     if (pl.from_seeds) {
-        if ((r = fs_seeds(h, desc, nb, TH, TW, TS, maxH, maxRows, vg, wg)) != CTWS_OK) return r;
+        // the filling size filter keeps the full uint64 ids (k_seeded.hip, value type V)
+        r = pl.sf_fill ? fs_seeds(h, desc, nb, TH, TW, TS, maxH, maxRows, vg, wg, uint64_t())
+                       : fs_seeds(h, desc, nb, TH, TW, TS, maxH, maxRows, vg, wg, uint32_t());
+        if (r != CTWS_OK) return r;
     } else {
     if (real_edt) {
         // vigra's real-valued path: double temporary (non-integer pitch) or float (dmax >= 2^24)
@@ -1392,7 +1412,12 @@ int run_batch(ctws_handle* h, const ctws_cfg* cfg, const Plan& pl, ctws_block* b
         if (!fused3) k_p2_excl<<<vg, 256, 0, h->stream>>>(w.desc, w.stat, w.sb, excl);
     } else if (pl.from_seeds) {
         // labels, keys and seed flags in the packed / wide key form (fs_seeds counted them)
-        k_fs_label<<<vg, 256, 0, h->stream>>>(w.desc, w.stat, w.hkey, w.hpos, w.hm, w.lab, w.key, w.cls, packed ? 1 : 0);
+        if (pl.sf_fill)
+            k_fs_label<uint64_t><<<vg, 256, 0, h->stream>>>(w.desc, w.stat, w.hkey, w.hpos, w.hm, w.lab, w.key, w.cls,
+                                                            packed ? 1 : 0);
+        else
+            k_fs_label<uint32_t><<<vg, 256, 0, h->stream>>>(w.desc, w.stat, w.hkey, w.hpos, w.hm, w.lab, w.key, w.cls,
+                                                            packed ? 1 : 0);
         k_fs_auto_label<<<vg, 256, 0, h->stream>>>(w.desc, w.stat, w.surv, w.W, w.Wp, w.hm, w.lab, w.key, w.cls,
                                                    packed ? 1 : 0);
     } else {
@@ -1704,8 +1729,14 @@ int run_batch(ctws_handle* h, const ctws_cfg* cfg, const Plan& pl, ctws_block* b
         // WatershedFromSeeds: labels -> seed values (uint64), masked voxels 0; no crop / offset
         mark("finalize");
         mark("crop_cc");
-        k_fs_output<<<vg, 256, 0, h->stream>>>(w.desc, w.stat, w.lab, w.key, keys_final, (const uint32_t*)h->fs_sorted.p,
-                                               w.surv, cfg->size_filter > 0 ? 1 : 0);
+        if (pl.sf_fill)
+            k_fs_output<uint64_t><<<vg, 256, 0, h->stream>>>(w.desc, w.stat, w.lab, w.key, keys_final,
+                                                             (const uint64_t*)h->fs_sorted.p, w.surv,
+                                                             cfg->size_filter > 0 ? 1 : 0);
+        else
+            k_fs_output<uint32_t><<<vg, 256, 0, h->stream>>>(w.desc, w.stat, w.lab, w.key, keys_final,
+                                                             (const uint32_t*)h->fs_sorted.p, w.surv,
+                                                             cfg->size_filter > 0 ? 1 : 0);
         LAUNCHCHK();
         mark("output");
     } else {
@@ -1879,6 +1910,7 @@ int run_batch(ctws_handle* h, const ctws_cfg* cfg, const Plan& pl, ctws_block* b
                           (err & kErrUnsupported) ? "auto-seeded regrow with >= 2^20 seeds " : "",
                           (err & kErrOverflow) ? "seed id >= 2^32 - 1: Overflow detected, as in the reference " : "",
                           (err & kErrVerify) ? "size-filter regrow fixpoint check failed " : "");
+            if (err & kErrReserved) h->err += "label 2^64 - 1 is reserved (the seed hash's empty marker) ";
             h->err += msg;
         }
     }
@@ -2314,7 +2346,7 @@ int run_blocks_host(ctws_handle* h, const ctws_cfg* cfg, const Plan& pl, ctws_bl
 }
 
 int run_blocks(ctws_handle* h, const ctws_cfg* cfg_in, ctws_block* blocks, int n, bool device_ptrs,
-               bool from_seeds = false) {
+               bool from_seeds = false, bool sf_fill = false) {
     if (!h || !cfg_in || (!blocks && n > 0) || n < 0) return CTWS_EINVAL;
     h->err.clear();
     h->timings.clear();
@@ -2347,6 +2379,7 @@ int run_blocks(ctws_handle* h, const ctws_cfg* cfg_in, ctws_block* blocks, int n
     int r = make_plan(h, cfg, pl);
     if (r != CTWS_OK) return r;
     pl.from_seeds = from_seeds ? 1 : 0;
+    pl.sf_fill = sf_fill ? 1 : 0;
     // blocks whose inner mask is empty are skipped entirely (watershed.py:290-297); the
     // host-pointer path checks this on the host, the device path on the caller's side
     std::vector<int> todo;
@@ -2502,7 +2535,8 @@ void ctws_close(ctws_handle* h) {
                     w.fstat, h->st_in.p, h->st_mask.p, h->st_init.p, h->st_out.p, h->rl_lab.p, h->rl_bits.p,
                     h->rl_cnt.p, h->rl_offs.p, h->rl_out.p, h->rl_keys.p, h->rl_vals.p, h->rl_red.p,
                     h->edt_fh.p, h->edt_scratch.p, h->p2_hint_dev.p, h->rl_sorted.p, h->rl_uniq.p, h->rl_counts.p, h->rl_tmp.p,
-                    h->fs_vals.p, h->fs_sorted.p, h->fs_off.p, h->fs_tmp.p, h->ev_ka.p, h->ev_ca.p, h->ev_kb.p,
+                    h->fs_vals.p, h->fs_sorted.p, h->fs_off.p, h->fs_tmp.p, h->sf_ids.p, h->sf_bits.p, h->sf_desc.p,
+                    h->sf_stat.p, h->sf_seeds.p, h->sf_lab.p, h->sf_hm.p, h->sf_out.p, h->ev_ka.p, h->ev_ca.p, h->ev_kb.p,
                     h->ev_cb.p, h->ev_kp.p, h->ev_cp.p, h->ev_state.p, h->ev_out.p, h->ev_stage.p,
                     w.fplat, w.plev, w.fseed, h->tc_P.p, h->tc_bits.p, h->tc_cnt.p, h->tc_offs.p, h->tc_woff.p,
                     h->tc_red.p, h->tc_in.p, h->tc_mask.p, h->tc_out.p, h->tc_raw.p, h->tc_tmp.p, h->tc_taps.p};
@@ -2653,6 +2687,233 @@ int ctws_ws_from_seeds(ctws_handle* h, const ctws_cfg* cfg, ctws_block* blocks, 
 
 int ctws_ws_from_seeds_device(ctws_handle* h, const ctws_cfg* cfg, ctws_block* blocks, int n_blocks) {
     return run_blocks(h, cfg, blocks, n_blocks, true, true);
+}
+
+// ---- SizeFilterWorkflow: BackgroundSizeFilter / FillingSizeFilter blocks ---------------------
+namespace {
+
+// a discard set whose id range is at most this wide is kept as a bitmap too (32 MiB)
+constexpr uint64_t kSfBitmapRange = 1ull << 28;
+
+size_t sf_al(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// One batch (blocks[idx[..]]): membership of every voxel's id in the resident discard set, the
+// per-block facts, and from them what apply_block does (background_size_filter.py:110-130,
+// filling_size_filter.py:112-136).  The blocks that need the fill run on the from_seeds plan
+// (run_blocks with sf_fill) with the zeroed labels as seeds.
+int sf_batch(ctws_handle* h, ctws_block* blocks, const std::vector<int>& idx, int fill, bool dev, std::string& errs,
+             std::vector<std::pair<const char*, float>>& timings) {
+    const int nb = (int)idx.size();
+    int r;
+    std::vector<int64_t> N(nb), off(nb);
+    int64_t T = 0, maxN = 0;
+    for (int i = 0; i < nb; ++i) {
+        const ctws_block& b = blocks[idx[i]];
+        N[i] = b.outer_shape[0] * b.outer_shape[1] * b.outer_shape[2];
+        off[i] = T;
+        T += N[i];
+        maxN = std::max(maxN, N[i]);
+    }
+    if ((r = grow(h, h->sf_seeds, sizeof(uint64_t) * (size_t)T)) != CTWS_OK) return r;
+    if ((r = grow(h, h->sf_desc, sizeof(SfBlock) * (size_t)nb)) != CTWS_OK) return r;
+    if ((r = grow(h, h->sf_stat, sizeof(BlockStat) * (size_t)nb)) != CTWS_OK) return r;
+    if (!dev && (r = grow(h, h->sf_lab, sizeof(uint64_t) * (size_t)T)) != CTWS_OK) return r;
+    uint64_t* seeds = (uint64_t*)h->sf_seeds.p;
+    std::vector<SfBlock> sd(nb);
+    for (int i = 0; i < nb; ++i) {
+        const ctws_block& b = blocks[idx[i]];
+        if (dev) {
+            sd[i].lab = b.initial_seeds;
+        } else {
+            uint64_t* l = (uint64_t*)h->sf_lab.p + off[i];
+            HIPCHK(copy_pieces(l, b.initial_seeds, sizeof(uint64_t) * (size_t)N[i], hipMemcpyHostToDevice, h->stream));
+            sd[i].lab = l;
+        }
+        sd[i].seeds = seeds + off[i];
+        sd[i].N = N[i];
+    }
+    HIPCHK(hipMemcpyAsync(h->sf_desc.p, sd.data(), sizeof(SfBlock) * nb, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(h->sf_stat.p, 0, sizeof(BlockStat) * nb, h->stream));
+    SfDiscard d;
+    d.ids = (const uint64_t*)h->sf_ids.p;
+    d.n = h->sf_n;
+    d.bits = h->sf_has_bits ? (const uint64_t*)h->sf_bits.p : nullptr;
+    d.lo = h->sf_n ? h->sf_lo : 1ull;
+    d.hi = h->sf_n ? h->sf_hi : 0ull;
+    record(h, 0);
+    const dim3 g((unsigned)std::max<int64_t>(1, std::min<int64_t>((maxN + 255) / 256, 4096)), nb);
+    k_sf_member<<<g, 256, 0, h->stream>>>((const SfBlock*)h->sf_desc.p, (BlockStat*)h->sf_stat.p, d);
+    LAUNCHCHK();
+    record(h, 1);
+    std::vector<BlockStat> st(nb);
+    HIPCHK(hipMemcpyAsync(st.data(), h->sf_stat.p, sizeof(BlockStat) * nb, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    {
+        float ms = 0.f;
+        hipEventElapsedTime(&ms, h->events[0], h->events[1]);
+        timings.push_back({"sf_member", ms});
+    }
+    // the fill's blocks: height maps and outputs on the device
+    std::vector<int> fi;
+    size_t hm_bytes = 0, out_elems = 0;
+    std::vector<size_t> hm_off(nb, 0), out_off(nb, 0);
+    for (int i = 0; i < nb; ++i) {
+        ctws_block& b = blocks[idx[i]];
+        b.n_ids = -1;
+        std::memcpy(&b.max_label, &st[i]._p[2], sizeof(uint64_t));
+        if (!st[i].active) {
+            b.status = CTWS_BLOCK_ZERO;  // every label 0: nothing written (:117-120)
+            b.max_label = 0;
+        } else if (!st[i].fg) {
+            b.status = CTWS_BLOCK_COPIED;  // no voxel carries a discard id: the labels (:123-128)
+            if (b.output != b.initial_seeds) {
+                if (dev) HIPCHK(copy_pieces(b.output, b.initial_seeds, sizeof(uint64_t) * (size_t)N[i], hipMemcpyDeviceToDevice, h->stream));
+                else std::memcpy(b.output, b.initial_seeds, sizeof(uint64_t) * (size_t)N[i]);
+            }
+        } else if (!fill) {
+            b.status = CTWS_BLOCK_WRITTEN;
+            HIPCHK(copy_pieces(b.output, seeds + off[i], sizeof(uint64_t) * (size_t)N[i],
+                               dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+        } else {
+            hm_off[i] = hm_bytes;
+            hm_bytes += sf_al((size_t)N[i] * (b.input_dtype == CTWS_U8 ? 1 : b.input_dtype == CTWS_U16 ? 2 : 4));
+            out_off[i] = out_elems;
+            out_elems += (size_t)N[i];
+            fi.push_back(i);
+        }
+    }
+    if (!fi.empty()) {
+        if (!dev) {
+            if ((r = grow(h, h->sf_hm, hm_bytes)) != CTWS_OK) return r;
+            if ((r = grow(h, h->sf_out, sizeof(uint64_t) * out_elems)) != CTWS_OK) return r;
+        }
+        std::vector<ctws_block> fb;
+        for (int i : fi) {
+            ctws_block b = blocks[idx[i]];
+            if (!dev) {
+                const size_t es = b.input_dtype == CTWS_U8 ? 1 : b.input_dtype == CTWS_U16 ? 2 : 4;
+                HIPCHK(copy_pieces((char*)h->sf_hm.p + hm_off[i], b.input, (size_t)N[i] * es, hipMemcpyHostToDevice,
+                                   h->stream));
+                b.input = (char*)h->sf_hm.p + hm_off[i];
+                b.output = (uint64_t*)h->sf_out.p + out_off[i];
+            }
+            b.initial_seeds = seeds + off[i];
+            b.mask = nullptr;
+            fb.push_back(b);
+        }
+        HIPCHK(hipStreamSynchronize(h->stream));
+        ctws_cfg cfg;
+        std::memset(&cfg, 0, sizeof(cfg));
+        cfg.channel_end = -1;
+        cfg.block_shape[0] = cfg.block_shape[1] = cfg.block_shape[2] = 1;
+        r = run_blocks(h, &cfg, fb.data(), (int)fb.size(), true, true, true);
+        errs += h->err;
+        for (auto& t : h->timings) timings.push_back(t);
+        if (r != CTWS_OK) return r;
+        for (size_t k = 0; k < fi.size(); ++k) {
+            ctws_block& b = blocks[idx[fi[k]]];
+            b.status = fb[k].status;
+            b.max_label = fb[k].max_label;
+            if (!dev && b.status == CTWS_BLOCK_WRITTEN)
+                HIPCHK(copy_pieces(b.output, fb[k].output, sizeof(uint64_t) * (size_t)N[fi[k]], hipMemcpyDeviceToHost,
+                                   h->stream));
+        }
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return CTWS_OK;
+}
+
+int sf_blocks(ctws_handle* h, ctws_block* blocks, int n, int fill, bool dev) {
+    if (!h || (!blocks && n > 0) || n < 0) return CTWS_EINVAL;
+    h->err.clear();
+    h->timings.clear();
+    HIPCHK(hipSetDevice(h->device));
+    std::string errs;
+    std::vector<int> todo;
+    for (int i = 0; i < n; ++i) {
+        ctws_block& b = blocks[i];
+        b.status = CTWS_BLOCK_WRITTEN;
+        b.n_ids = -1;
+        b.max_label = 0;
+        if (!b.initial_seeds || !b.output || (fill && !b.input)) {
+            h->err = "size filter blocks need labels (initial_seeds), an output and, for the fill, a height map (input)";
+            return CTWS_EINVAL;
+        }
+        for (int k = 0; k < 3; ++k)
+            if (b.outer_shape[k] <= 0 || b.inner_begin[k] != 0 || b.inner_shape[k] != b.outer_shape[k]) {
+                h->err = "size filter blocks have no halo: inner block == block";
+                return CTWS_EINVAL;
+            }
+        if (fill && (b.n_channels != 0 || (b.input_dtype != CTWS_U8 && b.input_dtype != CTWS_U16 && b.input_dtype != CTWS_F32))) {
+            b.status = CTWS_BLOCK_FAILED;
+            errs += "block " + std::to_string((long long)b.block_id) + " failed (the filling size filter takes a 3-D " +
+                    "uint8, uint16 or float32 height map: the flood runs on its float32 values exactly, which a " +
+                    (b.n_channels != 0 ? "multi-channel" : "float64 or other") + " map does not give); ";
+            continue;
+        }
+        todo.push_back(i);
+    }
+    std::vector<std::pair<const char*, float>> timings;
+    const int64_t budget = dev ? batch_voxels_budget() : std::min(batch_voxels_budget(), h->host_batch_voxels);
+    int r = CTWS_OK;
+    for (size_t k = 0; k < todo.size() && r == CTWS_OK;) {
+        std::vector<int> idx;
+        int64_t vox = 0;
+        while (k < todo.size()) {
+            const ctws_block& b = blocks[todo[k]];
+            const int64_t nv = b.outer_shape[0] * b.outer_shape[1] * b.outer_shape[2];
+            if (!idx.empty() && (vox + nv > budget || idx.size() >= 4096)) break;
+            vox += nv;
+            idx.push_back(todo[k++]);
+        }
+        r = sf_batch(h, blocks, idx, fill, dev, errs, timings);
+    }
+    const std::string last = h->err;
+    h->err = errs;
+    if (r != CTWS_OK && errs.find(last) == std::string::npos) h->err += last;
+    h->timings.clear();
+    for (auto& t : timings) add_timing(h, t.first, t.second);
+    return r;
+}
+
+}  // namespace
+
+int ctws_set_discard_u64(ctws_handle* h, const uint64_t* ids, int64_t n) {
+    if (!h || n < 0 || (n > 0 && !ids)) return CTWS_EINVAL;
+    h->err.clear();
+    HIPCHK(hipSetDevice(h->device));
+    for (int64_t i = 1; i < n; ++i)
+        if (ids[i] <= ids[i - 1]) {
+            h->err = "discard ids must be strictly ascending";
+            return CTWS_EINVAL;
+        }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->sf_n = 0;
+    h->sf_has_bits = false;
+    if (n == 0) return CTWS_OK;
+    int r;
+    if ((r = grow(h, h->sf_ids, sizeof(uint64_t) * (size_t)n)) != CTWS_OK) return r;
+    HIPCHK(hipMemcpy(h->sf_ids.p, ids, sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice));
+    const uint64_t lo = ids[0], hi = ids[n - 1];
+    if (hi - lo < kSfBitmapRange) {
+        std::vector<uint64_t> bits((size_t)((hi - lo) >> 6) + 1, 0ull);
+        for (int64_t i = 0; i < n; ++i) bits[(ids[i] - lo) >> 6] |= 1ull << ((ids[i] - lo) & 63);
+        if ((r = grow(h, h->sf_bits, sizeof(uint64_t) * bits.size())) != CTWS_OK) return r;
+        HIPCHK(hipMemcpy(h->sf_bits.p, bits.data(), sizeof(uint64_t) * bits.size(), hipMemcpyHostToDevice));
+        h->sf_has_bits = true;
+    }
+    h->sf_lo = lo;
+    h->sf_hi = hi;
+    h->sf_n = n;
+    return CTWS_OK;
+}
+
+int ctws_size_filter_blocks(ctws_handle* h, ctws_block* blocks, int n_blocks, int fill) {
+    return sf_blocks(h, blocks, n_blocks, fill ? 1 : 0, false);
+}
+
+int ctws_size_filter_blocks_device(ctws_handle* h, ctws_block* blocks, int n_blocks, int fill) {
+    return sf_blocks(h, blocks, n_blocks, fill ? 1 : 0, true);
 }
 
 int ctws_last_timings(const ctws_handle* h, const char** names, float* ms, int max_entries) {

@@ -74,6 +74,7 @@ constexpr uint32_t kErrTakeDict = 8u;    // pass 2: auto-seed label without a ne
 constexpr uint32_t kErrUnsupported = 16u; // (unused since round 6: the wide keys auto-seed their regrow too)
 constexpr uint32_t kErrVerify = 64u;     // the regrow's fixpoint check failed (CTWS_VERIFY=1): labels not written
 constexpr uint32_t kErrOverflow = 32u;    // WatershedFromSeeds: seed id >= 2^32 - 1 (the reference's assert)
+constexpr uint32_t kErrReserved = 128u;   // filling size filter: a label is 2^64 - 1, the seed hash's empty marker
 
 // Pointers read from the block descriptor are generic to the compiler: accesses through them
 // become flat loads, and the waits the compiler puts around flat accesses serialise a wave's

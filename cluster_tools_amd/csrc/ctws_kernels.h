@@ -196,18 +196,40 @@ __global__ void k_eval_reduce(const uint64_t*, const unsigned long long*, int64_
                               const unsigned long long*, double*);
 // k_seeded.hip (WatershedFromSeeds)
 __global__ void k_fs_active(const BlockDesc*, BlockStat*, int);
+// (V: uint32_t = WatershedFromSeeds' uint32 cast, uint64_t = the filling size filter's full ids)
+template <class V>
 __global__ void k_fs_insert(const BlockDesc*, BlockStat*, uint64_t*);
-__global__ void k_fs_collect(const BlockDesc*, BlockStat*, const uint64_t*, uint32_t*);
+template <class V>
+__global__ void k_fs_collect(const BlockDesc*, BlockStat*, const uint64_t*, V*);
 __global__ void k_fs_offsets(const BlockDesc*, const BlockStat*, int, int*, int*);
-__global__ void k_fs_rank(const BlockDesc*, const BlockStat*, const uint64_t*, const uint32_t*, uint32_t*);
+template <class V>
+__global__ void k_fs_rank(const BlockDesc*, const BlockStat*, const uint64_t*, const V*, uint32_t*);
+template <class V>
 __global__ void k_fs_label(const BlockDesc*, const BlockStat*, const uint64_t*, const uint32_t*, const float*, uint32_t*,
                            uint64_t*, uint8_t*, int);
 __global__ void k_fs_auto_label(const BlockDesc*, BlockStat*, const uint32_t*, const uint64_t*, const uint32_t*,
                                 const float*, uint32_t*, uint64_t*, uint8_t*, int);
-__global__ void k_fs_output(const BlockDesc*, BlockStat*, const uint32_t*, const uint64_t*, int, const uint32_t*,
+template <class V>
+__global__ void k_fs_output(const BlockDesc*, BlockStat*, const uint32_t*, const uint64_t*, int, const V*,
                             const uint32_t*, int);
 hipError_t fs_segmented_sort(void* tmp, size_t& bytes, const uint32_t* in, uint32_t* out, int n, int nseg,
                              const int* beg, const int* end, hipStream_t stream);
+hipError_t fs_segmented_sort(void* tmp, size_t& bytes, const uint64_t* in, uint64_t* out, int n, int nseg,
+                             const int* beg, const int* end, hipStream_t stream);
+// k_sizefilter.hip (postprocess SizeFilterWorkflow: membership in the discard set, raw height map)
+struct SfDiscard {
+    const uint64_t* ids;   // the discard ids, ascending
+    int64_t n;
+    const uint64_t* bits;  // a bitmap over [lo, hi] (bit id - lo) when the range is small, else nullptr
+    uint64_t lo, hi;       // ids[0], ids[n - 1]; an empty set has lo > hi
+};
+struct SfBlock {
+    const uint64_t* lab;  // the block's labels
+    uint64_t* seeds;      // out: the labels, 0 where discarded
+    int64_t N;
+};
+__global__ void k_sf_member(const SfBlock*, BlockStat*, SfDiscard);
+__global__ void k_sf_hmap(const BlockDesc*, float*);
 // per-chunk arrays (generations, queued marks) are indexed at fbase >> kChunkShift: a block's
 // frontier words hold at least 2^kChunkShift words per chunk (every brick is 64 words)
 constexpr int kChunkShift = 6;

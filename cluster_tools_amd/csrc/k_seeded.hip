@@ -13,6 +13,12 @@
 // same (C, d, value) fixpoint as on the raw values; the output maps labels back to values.
 // A block without any seed is seeded by vigra from the strict hmap minima (labels 1..n in
 // scan order, k_auto_minima + k_fs_auto_label); its labels are output as they are.
+//
+// The value type V of the kernels: uint32_t for WatershedFromSeeds (the reference casts the seeds
+// to uint32 after its overflow assert); uint64_t for the filling size filter (k_sizefilter.hip,
+// postprocess/filling_size_filter.py), whose labels are un-relabelled watershed ids
+// block_id * prod(block_shape) + k that pass 2^32 in large volumes.  The only reserved 64-bit
+// value is ~0, the hash's empty marker: a block that holds it fails (kErrReserved).
 #include <hipcub/hipcub.hpp>
 
 #include "ctws_kernels.h"
@@ -51,8 +57,10 @@ __global__ void k_fs_active(const BlockDesc* __restrict__ D, BlockStat* S, int n
     if (b < n) S[b].active = 1u;
 }
 
-// distinct nonzero seed values (uint32 after the overflow assert) -> the block's hash table.
-// A voxel whose scan predecessor along x holds the same value is skipped (runs insert once).
+// distinct nonzero seed values (uint32 after the overflow assert, or the full uint64) -> the
+// block's hash table.  A voxel whose scan predecessor along x holds the same value is skipped
+// (runs insert once).
+template <class V>
 __global__ void __launch_bounds__(256) k_fs_insert(const BlockDesc* __restrict__ D, BlockStat* S,
                                                    uint64_t* __restrict__ hkey) {
     const BlockDesc& B = D[blockIdx.y];
@@ -61,10 +69,17 @@ __global__ void __launch_bounds__(256) k_fs_insert(const BlockDesc* __restrict__
     uint32_t err = 0;
     FS_LOOP(i, B) {
         const uint64_t s64 = gbl(B.init)[i];
-        if (s64 >= 0xFFFFFFFFull) err |= kErrOverflow;  // "Overflow detected" (:160-163)
-        const uint32_t s = (uint32_t)s64;
+        if (sizeof(V) == 8) {
+            if (s64 == kFsEmpty) {
+                err |= kErrReserved;
+                continue;
+            }
+        } else if (s64 >= 0xFFFFFFFFull) {
+            err |= kErrOverflow;  // "Overflow detected" (:160-163)
+        }
+        const V s = (V)s64;
         if (!s) continue;
-        if (i % B.X && (uint32_t)gbl(B.init)[i - 1] == s) continue;
+        if (i % B.X && (V)gbl(B.init)[i - 1] == s) continue;
         int64_t p0 = (int64_t)(fs_mix(s) & (uint64_t)(cap - 1));
         bool done = false;
         for (int64_t p = 0; p < cap; ++p) {
@@ -82,8 +97,9 @@ __global__ void __launch_bounds__(256) k_fs_insert(const BlockDesc* __restrict__
 }
 
 // the table's values -> a dense list per block (vals[hbase .. hbase + n_seeds)); n_seeds counts
+template <class V>
 __global__ void __launch_bounds__(256) k_fs_collect(const BlockDesc* __restrict__ D, BlockStat* S,
-                                                    const uint64_t* __restrict__ hkey, uint32_t* __restrict__ vals) {
+                                                    const uint64_t* __restrict__ hkey, V* __restrict__ vals) {
     const BlockDesc& B = D[blockIdx.y];
     const int lane = threadIdx.x & 63;
     for (int64_t s0 = (int64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63); s0 < B.hcap;
@@ -95,7 +111,7 @@ __global__ void __launch_bounds__(256) k_fs_collect(const BlockDesc* __restrict_
         uint32_t base = 0;
         if (lane == 0) base = atomicAdd(&S[blockIdx.y].n_seeds, (uint32_t)__popcll(m));
         base = (uint32_t)__shfl((int)base, 0);
-        if (has) vals[B.hbase + base + __popcll(m & ((1ull << lane) - 1ull))] = (uint32_t)hkey[B.hbase + s];
+        if (has) vals[B.hbase + base + __popcll(m & ((1ull << lane) - 1ull))] = (V)hkey[B.hbase + s];
     }
 }
 
@@ -109,16 +125,17 @@ __global__ void k_fs_offsets(const BlockDesc* __restrict__ D, const BlockStat* S
 }
 
 // hash slot -> label = 1 + rank of its value among the sorted distinct values (in hpos)
+template <class V>
 __global__ void __launch_bounds__(256) k_fs_rank(const BlockDesc* __restrict__ D, const BlockStat* S,
-                                                 const uint64_t* __restrict__ hkey, const uint32_t* __restrict__ sorted,
+                                                 const uint64_t* __restrict__ hkey, const V* __restrict__ sorted,
                                                  uint32_t* __restrict__ hpos) {
     const BlockDesc& B = D[blockIdx.y];
     const int n = (int)S[blockIdx.y].n_seeds;
-    const uint32_t* sv = sorted + B.hbase;
+    const V* sv = sorted + B.hbase;
     for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < B.hcap; s += (int64_t)gridDim.x * blockDim.x) {
         const uint64_t k = hkey[B.hbase + s];
         if (k == kFsEmpty) continue;
-        const uint32_t v = (uint32_t)k;
+        const V v = (V)k;
         int lo = 0, hi = n;  // first index with sv[idx] >= v
         while (lo < hi) {
             const int mid = (lo + hi) >> 1;
@@ -131,13 +148,14 @@ __global__ void __launch_bounds__(256) k_fs_rank(const BlockDesc* __restrict__ D
 
 // seeds -> flood labels, keys and fixed flags (the pass-2 convention of k_p2_label: a seed's
 // lab carries kFixedBit, its key (h, 0, label))
+template <class V>
 __global__ void __launch_bounds__(256) k_fs_label(const BlockDesc* __restrict__ D, const BlockStat* S,
                                                   const uint64_t* __restrict__ hkey, const uint32_t* __restrict__ hpos,
                                                   const float* __restrict__ h, uint32_t* __restrict__ lab,
                                                   uint64_t* __restrict__ key, uint8_t* __restrict__ fixedv, int packed) {
     const BlockDesc& B = D[blockIdx.y];
     FS_LOOP(i, B) {
-        const uint32_t s = (uint32_t)gbl(B.init)[i];
+        const V s = (V)gbl(B.init)[i];
         const int64_t gi = B.base + i;
         if (!s) {
             lab[gi] = 0u;
@@ -186,15 +204,16 @@ __global__ void __launch_bounds__(256) k_fs_auto_label(const BlockDesc* __restri
 
 // final labels -> uint64 seed values (auto-seeded blocks: the labels), masked voxels 0; the
 // largest output id in _p[2..3]
+template <class V>
 __global__ void __launch_bounds__(256) k_fs_output(const BlockDesc* __restrict__ D, BlockStat* S,
                                                    const uint32_t* __restrict__ lab, const uint64_t* __restrict__ key,
-                                                   int keys_final, const uint32_t* __restrict__ sorted,
+                                                   int keys_final, const V* __restrict__ sorted,
                                                    const uint32_t* __restrict__ survivors, int use_surv) {
     const BlockDesc& B = D[blockIdx.y];
     BlockStat& st = S[blockIdx.y];
     if (st.err) return;  // a failed block writes nothing
     const bool raw = st._p[1] != 0u || (use_surv && !survivors[B.sbase]);
-    const uint32_t* sv = sorted + B.hbase;
+    const V* sv = sorted + B.hbase;
     uint64_t mx = 0;
     FS_LOOP(i, B) {
         const uint32_t l = flood_label(lab, key, keys_final, B.base + i);
@@ -216,5 +235,21 @@ hipError_t fs_segmented_sort(void* tmp, size_t& bytes, const uint32_t* in, uint3
                              const int* beg, const int* end, hipStream_t stream) {
     return hipcub::DeviceSegmentedRadixSort::SortKeys(tmp, bytes, in, out, n, nseg, beg, end, 0, 32, stream);
 }
+hipError_t fs_segmented_sort(void* tmp, size_t& bytes, const uint64_t* in, uint64_t* out, int n, int nseg,
+                             const int* beg, const int* end, hipStream_t stream) {
+    return hipcub::DeviceSegmentedRadixSort::SortKeys(tmp, bytes, in, out, n, nseg, beg, end, 0, 64, stream);
+}
+
+#define FS_INSTANTIATE(V)                                                                                         \
+    template __global__ void k_fs_insert<V>(const BlockDesc*, BlockStat*, uint64_t*);                             \
+    template __global__ void k_fs_collect<V>(const BlockDesc*, BlockStat*, const uint64_t*, V*);                  \
+    template __global__ void k_fs_rank<V>(const BlockDesc*, const BlockStat*, const uint64_t*, const V*, uint32_t*); \
+    template __global__ void k_fs_label<V>(const BlockDesc*, const BlockStat*, const uint64_t*, const uint32_t*,  \
+                                           const float*, uint32_t*, uint64_t*, uint8_t*, int);                    \
+    template __global__ void k_fs_output<V>(const BlockDesc*, BlockStat*, const uint32_t*, const uint64_t*, int,  \
+                                            const V*, const uint32_t*, int);
+FS_INSTANTIATE(uint32_t)
+FS_INSTANTIATE(uint64_t)
+#undef FS_INSTANTIATE
 
 }  // namespace ctws

@@ -11,6 +11,7 @@ import threading
 import numpy as np
 
 from ._abi import CtwsBlock, make_cfg, dtype_code, CTWS_OK, CTWS_BLOCK_FAILED, CTWS_BLOCK_WRITTEN  # noqa: F401
+from ._abi import CTWS_BLOCK_ZERO, CTWS_BLOCK_COPIED, CTWS_F64  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # CTWS_LIB: another build of the library (A/B of build variants in one process tree)
@@ -60,6 +61,9 @@ def lib():
                                           C.c_int64, C.POINTER(C.c_int64)]
             L.ctws_set_table_u64.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
             L.ctws_ufd_find.argtypes = [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
+            L.ctws_set_discard_u64.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+            L.ctws_size_filter_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+            L.ctws_size_filter_blocks_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
             L.ctws_threshold_components.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                                     C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p,
                                                     C.POINTER(C.c_int64)]
@@ -83,7 +87,8 @@ EXPORTED_SYMBOLS = ('ctws_abi_version', 'ctws_open', 'ctws_close', 'ctws_last_er
                     'ctws_ws_blocks_device', 'ctws_last_timings', 'ctws_unique_u64', 'ctws_unique_counts_u64', 'ctws_set_table_u64', 'ctws_lookup_u64',
                     'ctws_debug_set_stop', 'ctws_debug_read', 'ctws_debug_sqrt_int', 'ctws_ws_from_seeds', 'ctws_ws_from_seeds_device',
                     'ctws_eval_begin', 'ctws_eval_add', 'ctws_eval_end', 'ctws_threshold_components',
-                    'ctws_threshold_components_ex', 'ctws_ufd_find')
+                    'ctws_threshold_components_ex', 'ctws_ufd_find', 'ctws_set_discard_u64', 'ctws_size_filter_blocks',
+                    'ctws_size_filter_blocks_device')
 
 
 def ufd_find(n_labels, pairs):
@@ -292,6 +297,91 @@ class Handle:
             c.output = out.ctypes.data
             results.append({'output': out})
         self._check(lib().ctws_ws_from_seeds(self._h, C.byref(cfg), arr, n), 'ctws_ws_from_seeds')
+        for i, r in enumerate(results):
+            r['status'] = int(arr[i].status)
+            r['max_label'] = int(arr[i].max_label)
+        return results
+
+    # ---- SizeFilterWorkflow ---------------------------------------------------------------
+    def set_discard_ids(self, ids):
+        """Upload the discard ids (discard_ids.npy of SizeFilterBlocks: ascending, unique) and
+        keep them resident on the GPU; an empty list clears the set."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint64).ravel()
+        self._check(lib().ctws_set_discard_u64(self._h, ids.ctypes.data if ids.size else None, ids.size),
+                    'ctws_set_discard_u64')
+
+    def size_filter_blocks(self, blocks, fill=False):
+        """`apply_block` of BackgroundSizeFilter (fill=False) or FillingSizeFilter (fill=True) on
+        numpy blocks: dicts with 'labels' (the block's ids, as ds_in[bb] returns them), 'hmap'
+        (the block's raw height map, uint8 / uint16 / float32; fill only) and optional 'out'
+        (uint64, block-shaped; may be the labels array itself).  The discard ids are those of
+        set_discard_ids.  Returns [{'output', 'status', 'max_label'}, ...]; the output of a block
+        with status CTWS_BLOCK_ZERO or CTWS_BLOCK_FAILED is not written."""
+        n = len(blocks)
+        arr = (CtwsBlock * n)()
+        keep, results = [], []
+        for i, b in enumerate(blocks):
+            labels = np.ascontiguousarray(b['labels'], dtype=np.uint64)
+            assert labels.ndim == 3, labels.shape
+            shape = labels.shape
+            c = arr[i]
+            c.initial_seeds = labels.ctypes.data
+            c.outer_shape[:] = list(shape)
+            c.inner_shape[:] = list(shape)
+            c.block_id = int(b.get('block_id', i))
+            keep.append(labels)
+            if fill:
+                hmap = np.ascontiguousarray(b['hmap'])
+                assert hmap.shape == shape, (hmap.shape, shape)
+                c.input = hmap.ctypes.data
+                c.input_dtype = dtype_code(hmap.dtype)
+                keep.append(hmap)
+            out = b.get('out')
+            if out is None:
+                out = np.zeros(shape, dtype=np.uint64)
+            assert out.dtype == np.uint64 and out.flags.c_contiguous and out.shape == shape
+            keep.append(out)
+            c.output = out.ctypes.data
+            results.append({'output': out})
+        self._check(lib().ctws_size_filter_blocks(self._h, arr, n, int(bool(fill))), 'ctws_size_filter_blocks')
+        for i, r in enumerate(results):
+            r['status'] = int(arr[i].status)
+            r['max_label'] = int(arr[i].max_label)
+        return results
+
+    def size_filter_blocks_device(self, blocks, fill=False):
+        """size_filter_blocks on torch tensors on this GPU: 'labels' and 'out' int64 / uint64
+        tensors (allocated if 'out' is missing), 'hmap' uint8 / uint16 / float32.  Nothing but the
+        per-block facts crosses PCIe.  Returns [{'output', 'status', 'max_label'}, ...]."""
+        import torch
+        codes = {'torch.uint8': 1, 'torch.uint16': 2, 'torch.float32': 3, 'torch.float64': 4}
+        n = len(blocks)
+        arr = (CtwsBlock * n)()
+        results = []
+        for i, b in enumerate(blocks):
+            labels = b['labels']
+            assert labels.is_cuda and labels.is_contiguous() and labels.element_size() == 8 and labels.dim() == 3
+            c = arr[i]
+            c.initial_seeds = labels.data_ptr()
+            c.outer_shape[:] = list(labels.shape)
+            c.inner_shape[:] = list(labels.shape)
+            c.block_id = int(b.get('block_id', i))
+            if fill:
+                hmap = b['hmap']
+                assert hmap.is_cuda and hmap.is_contiguous() and tuple(hmap.shape) == tuple(labels.shape)
+                c.input = hmap.data_ptr()
+                c.input_dtype = codes[str(hmap.dtype)]
+            out = b.get('out')
+            if out is None:
+                out = torch.zeros(labels.shape, dtype=labels.dtype, device=labels.device)
+            assert out.is_cuda and out.is_contiguous() and out.element_size() == 8
+            assert tuple(out.shape) == tuple(labels.shape)
+            c.output = out.data_ptr()
+            results.append({'output': out})
+        if blocks:
+            torch.cuda.current_stream(blocks[0]['labels'].device).synchronize()
+        self._check(lib().ctws_size_filter_blocks_device(self._h, arr, n, int(bool(fill))),
+                    'ctws_size_filter_blocks_device')
         for i, r in enumerate(results):
             r['status'] = int(arr[i].status)
             r['max_label'] = int(arr[i].max_label)

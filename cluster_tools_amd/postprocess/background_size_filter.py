@@ -1,0 +1,171 @@
+#! /usr/bin/env python
+"""BackgroundSizeFilter: the ids in discard_ids.npy become 0, block by block on the GPU
+(cluster_tools/postprocess/background_size_filter.py:16-189; task surface, config keys and log
+lines unchanged).  `run_filter_blocks` is the job loop it shares with FillingSizeFilter; it
+follows watershed_from_seeds.run_seeded_blocks: one library handle per job, the discard ids
+uploaded once, blocks in batches with a read-ahead thread, outputs written and "processed block"
+logged in block-list order."""
+import json
+import os
+import sys
+from concurrent import futures
+
+import numpy as np
+
+from cluster_tools_amd import luigi_compat as luigi
+import cluster_tools_amd.utils.volume_utils as vu
+import cluster_tools_amd.utils.function_utils as fu
+from cluster_tools_amd.utils.blocking import Blocking
+from cluster_tools_amd.cluster_tasks import SlurmTask, LocalTask, LSFTask
+
+
+class BackgroundSizeFilterBase(luigi.Task):
+    task_name = 'background_size_filter'
+    src_file = os.path.abspath(__file__)
+
+    input_path = luigi.Parameter()
+    input_key = luigi.Parameter()
+    output_path = luigi.Parameter()
+    output_key = luigi.Parameter()
+    dependency = luigi.TaskParameter()
+
+    def requires(self):
+        return self.dependency
+
+    def _parse_log(self, log_path):
+        return parse_discard_path(log_path)
+
+    def run_impl(self):
+        shebang, block_shape, roi_begin, roi_end = self.global_config_values()
+        self.init(shebang)
+        shape = vu.get_shape(self.input_path, self.input_key)
+        block_list = self.blocks_to_process(shape, block_shape, roi_begin, roi_end)
+        chunks = tuple(bs // 2 for bs in block_shape)
+        with vu.file_reader(self.output_path) as f:
+            if self.output_key in f:
+                chunks = f[self.output_key].chunks
+            f.require_dataset(self.output_key, shape=shape, chunks=chunks, dtype='uint64', compression='gzip')
+        # the job config holds the paths only, as in the reference
+        config = {'input_path': self.input_path, 'input_key': self.input_key,
+                  'output_path': self.output_path, 'output_key': self.output_key,
+                  'block_shape': block_shape, 'res_path': self._parse_log(self.input().path)}
+        self.run_jobs(min(len(block_list), self.max_jobs), block_list, config)
+
+
+class BackgroundSizeFilterLocal(BackgroundSizeFilterBase, LocalTask):
+    pass
+
+
+class BackgroundSizeFilterSlurm(BackgroundSizeFilterBase, SlurmTask):
+    pass
+
+
+class BackgroundSizeFilterLSF(BackgroundSizeFilterBase, LSFTask):
+    pass
+
+
+#
+# Implementation
+#
+
+def parse_discard_path(log_path):
+    """The path SizeFilterBlocks logged ("saving results to ...", third-last line of its task log)."""
+    lines = [' '.join(ll.split()[2:]) for ll in fu.tail(log_path, 3)]
+    if lines and lines[0].startswith("saving results to"):
+        path = lines[0].split()[-1]
+        assert os.path.exists(path), path
+        return path
+    raise RuntimeError("Could not parse log file.")
+
+
+def _device():
+    return int(os.environ.get('CTWS_DEVICE', os.environ.get('LOCAL_RANK', '0')))
+
+
+def _read_block(blocking, block_id, ds_in, ds_hmap):
+    bb = vu.block_to_bb(blocking.getBlock(block_id))
+    b = {'block_id': block_id, 'bb': bb, 'labels': ds_in[bb]}
+    if ds_hmap is not None:
+        # a 4-D height map: its channel 0, as the reference's `(slice(0, 1),) + bb`
+        b['hmap'] = ds_hmap[(slice(0, 1),) + bb][0] if ds_hmap.ndim == 4 else ds_hmap[bb]
+    return b
+
+
+def run_filter_blocks(blocking, block_list, ds_in, ds_out, discard_ids, ds_hmap=None, batch_blocks=16):
+    """`apply_block` for every block of the job (background_size_filter.py:110-130; with a height
+    map filling_size_filter.py:112-136): nothing is written for an all-zero block, the labels for
+    a block without a discard id, else the filtered / filled labels."""
+    from cluster_tools_amd import ctws
+    fill = ds_hmap is not None
+    batches = [block_list[k:k + batch_blocks] for k in range(0, len(block_list), batch_blocks)]
+
+    def read_batch(ids):
+        return [_read_block(blocking, bid, ds_in, ds_hmap) for bid in ids]
+
+    with ctws.Handle(_device()) as h, futures.ThreadPoolExecutor(1) as io:
+        h.set_discard_ids(discard_ids)
+        nxt = io.submit(read_batch, batches[0]) if batches else None
+        for bi in range(len(batches)):
+            blocks = nxt.result()
+            # (in place the next batch is read while this one is written: other blocks, so no race)
+            nxt = io.submit(read_batch, batches[bi + 1]) if bi + 1 < len(batches) else None
+            for b in blocks:
+                fu.log("start processing block %i" % b['block_id'])
+            res = h.size_filter_blocks(blocks, fill=fill)
+            error = h.last_error()
+            for b, r in zip(blocks, res):
+                if r['status'] == ctws.CTWS_BLOCK_FAILED:
+                    raise ctws.CtwsError("block %i: %s" % (b['block_id'], error))
+                if r['status'] != ctws.CTWS_BLOCK_ZERO:
+                    ds_out[b['bb']] = r['output']
+                fu.log_block_success(b['block_id'])
+
+
+def run_filter_job(job_id, config, with_hmap):
+    """The job entry both filters share: the in-place, same-file and two-file cases, and the copy
+    of the 'maxId' attribute by job 0 when not in place."""
+    input_path, input_key = config['input_path'], config['input_key']
+    output_path, output_key = config['output_path'], config['output_key']
+    discard_ids = np.load(config['res_path'])
+    fu.log("Discarding %i ids" % len(discard_ids))
+    same_file = input_path == output_path
+    in_place = same_file and input_key == output_key
+    f_h = vu.file_reader(config['hmap_path'], 'r') if with_hmap else None
+    try:
+        ds_hmap = f_h[config['hmap_key']] if with_hmap else None
+        if same_file:
+            with vu.file_reader(input_path) as f:
+                ds_in = f[input_key]
+                ds_out = ds_in if in_place else f[output_key]
+                blocking = Blocking([0, 0, 0], list(ds_in.shape), list(config['block_shape']))
+                run_filter_blocks(blocking, config['block_list'], ds_in, ds_out, discard_ids, ds_hmap)
+        else:
+            with vu.file_reader(input_path, 'r') as f_in, vu.file_reader(output_path) as f_out:
+                ds_in, ds_out = f_in[input_key], f_out[output_key]
+                blocking = Blocking([0, 0, 0], list(ds_in.shape), list(config['block_shape']))
+                run_filter_blocks(blocking, config['block_list'], ds_in, ds_out, discard_ids, ds_hmap)
+    finally:
+        if f_h is not None:
+            f_h.close()
+    if job_id == 0 and not in_place:
+        with vu.file_reader(input_path, 'r') as f:
+            max_id = f[input_key].attrs.get('maxId', None)
+        if max_id is not None:
+            with vu.file_reader(output_path) as f:
+                f[output_key].attrs['maxId'] = max_id
+
+
+def background_size_filter(job_id, config_path):
+    fu.log("start processing job %i" % job_id)
+    fu.log("reading config from %s" % config_path)
+    with open(config_path) as f:
+        config = json.load(f)
+    run_filter_job(job_id, config, with_hmap=False)
+    fu.log_job_success(job_id)
+
+
+if __name__ == '__main__':
+    path = sys.argv[1]
+    assert os.path.exists(path), path
+    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
+    background_size_filter(job_id, path)

@@ -92,6 +92,9 @@ extern "C" {
 #define CTWS_BLOCK_FAILED       4  /* the block cannot be finished: nothing written;    */
                                    /* the reason is in ctws_last_error (the reference   */
                                    /* job would raise at this block)                    */
+/* further statuses of ctws_size_filter_blocks */
+#define CTWS_BLOCK_ZERO         5  /* every label is 0: nothing written                 */
+#define CTWS_BLOCK_COPIED       6  /* no voxel carries a discard id: output = labels    */
 
 /*
  * Task configuration.  Mirrors the watershed task config keys
@@ -183,6 +186,33 @@ int ctws_ws_blocks_device(ctws_handle* h, const ctws_cfg* cfg, ctws_block* block
  */
 int ctws_ws_from_seeds(ctws_handle* h, const ctws_cfg* cfg, ctws_block* blocks, int n_blocks);
 int ctws_ws_from_seeds_device(ctws_handle* h, const ctws_cfg* cfg, ctws_block* blocks, int n_blocks);
+
+/*
+ * SizeFilterWorkflow (postprocess/postprocess_workflow.py:24-112): the block loops of
+ * BackgroundSizeFilter (background_size_filter.py:110-130) and FillingSizeFilter
+ * (filling_size_filter.py:112-136, `apply_block`).
+ *
+ * ctws_set_discard_u64: upload the discard ids (host, strictly ascending; discard_ids.npy of
+ *   SizeFilterBlocks) and keep them resident on the handle; n = 0 clears the set.  The set is a
+ *   sorted table, and a bitmap over [ids[0], ids[n - 1]] too when that range is below 2^28.
+ * ctws_size_filter_blocks / _device: per block, `initial_seeds` = the block's uint64 labels
+ *   (ds_in[bb]; no halo: inner_begin = 0, inner_shape = outer_shape), `output` = the uint64
+ *   result (may be the labels' own buffer), and with fill = 1 `input` = the RAW height map of
+ *   the block (CTWS_U8 / U16 / F32, n_channels 0; a float64 or multi-channel map gives
+ *   CTWS_BLOCK_FAILED with the reason).  Host pointers, or device pointers for _device.
+ *     every label 0              -> CTWS_BLOCK_ZERO, nothing written
+ *     no voxel in the discard set -> CTWS_BLOCK_COPIED, output = labels
+ *     else                        -> CTWS_BLOCK_WRITTEN: labels with the discarded ids set to 0
+ *       (fill = 0), or watershedsNew(float32(input), seeds = those labels) (fill = 1; 3-D direct
+ *       nbhd; the height map is NOT normalized and the ids keep their full 64 bits, flooded as
+ *       order-preserving compact labels; a block without any label left is seeded by vigra
+ *       from the strict minima of the height map and gets ids 1..n, as in the reference).
+ *   max_label = the largest output id.  The only reserved id is 2^64 - 1 (fill = 1:
+ *   CTWS_BLOCK_FAILED).  mask, block_id (messages only) and cfg-like fields are not read.
+ */
+int ctws_set_discard_u64(ctws_handle* h, const uint64_t* ids, int64_t n);
+int ctws_size_filter_blocks(ctws_handle* h, ctws_block* blocks, int n_blocks, int fill);
+int ctws_size_filter_blocks_device(ctws_handle* h, ctws_block* blocks, int n_blocks, int fill);
 
 /*
  * Evaluation (evaluation/measures.py:80-164 with utils/validation_utils.py:60-76, 178-198):
