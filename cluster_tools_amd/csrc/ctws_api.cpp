@@ -126,6 +126,10 @@ struct ctws_handle {
     // [ids[0], ids[n - 1]] when that range is small), the blocks' descriptors, facts and seeds
     // (labels with the discarded ids zeroed), host-pointer staging of labels / height maps / outputs
     DevBuf sf_ids, sf_bits, sf_desc, sf_stat, sf_seeds, sf_lab, sf_hm, sf_out;
+    // GraphWorkflow (k_rag.hip): host-pointer staging of labels / pairs / weights, the sorted
+    // endpoint table, the emitted node ids, pairs and weights, keys (then the unique keys), sorted keys and
+    // weights, summed weights, unpacked edges, sort / reduce temp, counters (append, runs, missing)
+    DevBuf rg_lab, rg_tab, rg_nodes, rg_pairs, rg_w, rg_keys, rg_skeys, rg_sw, rg_sum, rg_out, rg_tmp, rg_red;
     int64_t sf_n = 0;
     uint64_t sf_lo = 1, sf_hi = 0;
     bool sf_has_bits = false;
@@ -2539,7 +2543,9 @@ void ctws_close(ctws_handle* h) {
                     h->sf_stat.p, h->sf_seeds.p, h->sf_lab.p, h->sf_hm.p, h->sf_out.p, h->ev_ka.p, h->ev_ca.p, h->ev_kb.p,
                     h->ev_cb.p, h->ev_kp.p, h->ev_cp.p, h->ev_state.p, h->ev_out.p, h->ev_stage.p,
                     w.fplat, w.plev, w.fseed, h->tc_P.p, h->tc_bits.p, h->tc_cnt.p, h->tc_offs.p, h->tc_woff.p,
-                    h->tc_red.p, h->tc_in.p, h->tc_mask.p, h->tc_out.p, h->tc_raw.p, h->tc_tmp.p, h->tc_taps.p};
+                    h->tc_red.p, h->tc_in.p, h->tc_mask.p, h->tc_out.p, h->tc_raw.p, h->tc_tmp.p, h->tc_taps.p,
+                    h->rg_lab.p, h->rg_tab.p, h->rg_nodes.p, h->rg_pairs.p, h->rg_w.p, h->rg_keys.p, h->rg_skeys.p, h->rg_sw.p,
+                    h->rg_sum.p, h->rg_out.p, h->rg_tmp.p, h->rg_red.p};
     for (void* p : ptrs)
         if (p) hipFree(p);
     for (auto e : h->events) hipEventDestroy(e);
@@ -3172,6 +3178,267 @@ int ctws_lookup_u64(ctws_handle* h, uint64_t* labels, int64_t n, int on_device, 
     HIPCHK(hipStreamSynchronize(h->stream));
     if (n_missing) *n_missing = (int64_t)hm;
     return CTWS_OK;
+}
+
+// ---- GraphWorkflow: the region adjacency graph (k_rag.hip) ----------------------------------
+extern "C++" {
+namespace {
+constexpr size_t kRagRed = 32;  // counter words of rg_red
+
+// the stage between events a and b of this call, in ms
+void rag_time(ctws_handle* h, const char* name, size_t a, size_t b) {
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, h->events[a], h->events[b]) == hipSuccess) add_timing(h, name, ms);
+}
+
+// The sorted distinct values of dv (device) into rg_tab, by the relabel path's radix sort and
+// run-length encoding: these are id tables with many repeats of few values over a narrow range,
+// where the bitmap unique's atomics all land in a few words (57 ms for the 16.8 M labels of a
+// block of fragments, measured).  The table grows to the size the first call reports.
+int rag_table(ctws_handle* h, const uint64_t* dv, int64_t n, int64_t* nt) {
+    int r;
+    *nt = 0;
+    if (n == 0) return CTWS_OK;
+    const int64_t cap = std::max<int64_t>((int64_t)(h->rg_tab.bytes / sizeof(uint64_t)), 1 << 16);
+    if ((r = grow(h, h->rg_tab, sizeof(uint64_t) * (size_t)cap)) != CTWS_OK) return r;
+    r = unique_sorted(h, dv, n, 1, (uint64_t*)h->rg_tab.p, nullptr, cap, nt);
+    if (r == CTWS_EINVAL && *nt > cap) {
+        const int64_t want = *nt;
+        h->err.clear();
+        if ((r = grow(h, h->rg_tab, sizeof(uint64_t) * (size_t)want)) != CTWS_OK) return r;
+        r = unique_sorted(h, dv, n, 1, (uint64_t*)h->rg_tab.p, nullptr, want, nt);
+    }
+    return r;
+}
+
+// The tail both entry points share: n (pair, weight) records on the device -> the sorted unique
+// pairs in rg_out (m x 2) with their summed weights in rg_sum (m).  tab (device, ascending)
+// holds every endpoint value; weights == nullptr counts 1 per record.
+int pairs_tail(ctws_handle* h, const uint64_t* pairs, const uint64_t* weights, int64_t n, const uint64_t* tab,
+               int64_t nt, int64_t* m) {
+    *m = 0;
+    if (n == 0) return CTWS_OK;
+    if (n >= (1ll << 31)) {
+        h->err = "unique pairs: more than 2^31 - 1 pairs in one call";
+        return CTWS_EUNSUPPORTED;
+    }
+    if (nt >= (1ll << 32)) {
+        h->err = "unique pairs: 2^32 or more distinct ids in one call (the sort keys hold two 32-bit ranks)";
+        return CTWS_EUNSUPPORTED;
+    }
+    int b = 1;  // bits per rank
+    while ((1ll << b) < nt) ++b;
+    int r;
+    const size_t nb = sizeof(uint64_t) * (size_t)n;
+    size_t tb_sort = 0, tb_red = 0;
+    HIPCHK(pair_sort(nullptr, tb_sort, nullptr, nullptr, nullptr, nullptr, n, 2 * b, h->stream));
+    HIPCHK(pair_reduce(nullptr, tb_red, nullptr, nullptr, nullptr, nullptr, nullptr, n, h->stream));
+    if ((r = grow(h, h->rg_keys, nb)) != CTWS_OK) return r;
+    if ((r = grow(h, h->rg_skeys, nb)) != CTWS_OK) return r;
+    if ((r = grow(h, h->rg_sw, nb)) != CTWS_OK) return r;
+    if ((r = grow(h, h->rg_sum, nb)) != CTWS_OK) return r;
+    if ((r = grow(h, h->rg_tmp, std::max(tb_sort, tb_red))) != CTWS_OK) return r;
+    if ((r = grow(h, h->rg_red, kRagRed * sizeof(uint64_t))) != CTWS_OK) return r;
+    if (!weights && (r = grow(h, h->rg_w, nb)) != CTWS_OK) return r;
+    uint64_t* keys = (uint64_t*)h->rg_keys.p;
+    uint64_t* skeys = (uint64_t*)h->rg_skeys.p;
+    uint64_t* sw = (uint64_t*)h->rg_sw.p;
+    uint64_t* sums = (uint64_t*)h->rg_sum.p;
+    unsigned long long* red = (unsigned long long*)h->rg_red.p;  // [1] runs, [2] missing
+    const unsigned g = (unsigned)std::min<int64_t>((n + 255) / 256, 8192);
+    HIPCHK(hipMemsetAsync(red + 1, 0, 2 * sizeof(uint64_t), h->stream));
+    record(h, 2);
+    if (!weights) {
+        k_pair_ones<<<g, 256, 0, h->stream>>>((uint64_t*)h->rg_w.p, n);
+        weights = (const uint64_t*)h->rg_w.p;
+    }
+    k_pair_keys<<<g, 256, 0, h->stream>>>(pairs, n, tab, nt, b, keys, red + 2);
+    LAUNCHCHK();
+    record(h, 3);
+    HIPCHK(pair_sort(h->rg_tmp.p, tb_sort, keys, skeys, weights, sw, n, 2 * b, h->stream));
+    record(h, 4);
+    // (the unsorted keys are dead: their buffer takes the unique keys)
+    HIPCHK(pair_reduce(h->rg_tmp.p, tb_red, skeys, keys, sw, sums, (uint64_t*)(red + 1), n, h->stream));
+    record(h, 5);
+    unsigned long long hr[2] = {0ull, 0ull};
+    HIPCHK(hipMemcpyAsync(hr, red + 1, sizeof(hr), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (hr[1]) {
+        h->err = "unique pairs: " + std::to_string(hr[1]) + " endpoint values are missing from the id table";
+        return CTWS_EINVAL;
+    }
+    *m = (int64_t)hr[0];
+    if ((r = grow(h, h->rg_out, 2 * sizeof(uint64_t) * (size_t)*m)) != CTWS_OK) return r;
+    const unsigned gm = (unsigned)std::min<int64_t>((*m + 255) / 256, 8192);
+    k_pair_unpack<<<gm, 256, 0, h->stream>>>(keys, *m, tab, b, (uint64_t*)h->rg_out.p);
+    LAUNCHCHK();
+    record(h, 6);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    rag_time(h, "pair_keys", 2, 3);
+    rag_time(h, "pair_sort", 3, 4);
+    rag_time(h, "pair_reduce", 4, 5);
+    rag_time(h, "pair_unpack", 5, 6);
+    return CTWS_OK;
+}
+
+// the tail's result -> the caller's buffers (the sizes are known to fit)
+int pairs_out(ctws_handle* h, int64_t m, int on_device, uint64_t* out, uint64_t* counts) {
+    if (m) {
+        const hipMemcpyKind k = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+        HIPCHK(hipMemcpyAsync(out, h->rg_out.p, 2 * sizeof(uint64_t) * (size_t)m, k, h->stream));
+        if (counts) HIPCHK(hipMemcpyAsync(counts, h->rg_sum.p, sizeof(uint64_t) * (size_t)m, k, h->stream));
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return CTWS_OK;
+}
+
+int rag_block(ctws_handle* h, const uint64_t* labels, int64_t nz, int64_t ny, int64_t nx, int ignore_label,
+              uint64_t* nodes, int64_t cap_nodes, int64_t* n_nodes, uint64_t* edges, uint64_t* counts,
+              int64_t cap_edges, int64_t* n_edges, bool dev) {
+    if (!h || !labels || nz <= 0 || ny <= 0 || nx <= 0 || !n_nodes || !n_edges || cap_nodes < 0 || cap_edges < 0 ||
+        (!nodes && cap_nodes > 0) || (!edges && cap_edges > 0))
+        return CTWS_EINVAL;
+    h->err.clear();
+    h->timings.clear();
+    HIPCHK(hipSetDevice(h->device));
+    *n_nodes = *n_edges = 0;
+    constexpr int64_t kMax = 1ll << 31;
+    if (nz >= kMax || ny >= kMax || nx >= kMax || nz * ny >= kMax || nz * ny * nx >= kMax) {
+        h->err = "rag block: 2^31 or more voxels in one block (the pair kernel indexes a block with 32 bits)";
+        return CTWS_EUNSUPPORTED;
+    }
+    const int64_t N = nz * ny * nx;
+    int r;
+    const uint64_t* dl = labels;
+    if (!dev) {
+        if ((r = grow(h, h->rg_lab, sizeof(uint64_t) * (size_t)N)) != CTWS_OK) return r;
+        HIPCHK(copy_pieces(h->rg_lab.p, labels, sizeof(uint64_t) * (size_t)N, hipMemcpyHostToDevice, h->stream));
+        dl = (const uint64_t*)h->rg_lab.p;
+    }
+    // one pass emits the pairs and the node ids.  First buffers of a quarter / a sixteenth of the
+    // voxels (the sizes depend on the block alone, so a call behaves the same whatever the handle
+    // ran before); the emission is repeated with the counted sizes when one did not fit
+    if ((r = grow(h, h->rg_red, kRagRed * sizeof(uint64_t))) != CTWS_OK) return r;
+    // [0] pairs, [16] nodes: a 128-B line each (the appends of all waves meet in these two words)
+    unsigned long long* cnt = (unsigned long long*)h->rg_red.p;
+    RagArgs a;
+    a.lab = dl;
+    a.nz = (uint32_t)nz;
+    a.ny = (uint32_t)ny;
+    a.nx = (uint32_t)nx;
+    a.ignore = ignore_label ? 1 : 0;
+    a.count = cnt;
+    a.ncount = cnt + 16;
+    const int64_t rows = nz * ny;
+    // four workgroups per CU (their LDS stages) and no more: every wave ends with an append of
+    // its own, and one counter word takes only ~85 returning atomics per microsecond
+    const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>((rows + 3) / 4, 1024));
+    unsigned long long emitted[17] = {0};
+    unsigned long long cap = (unsigned long long)std::max<int64_t>(64, N / 4);
+    unsigned long long ncap = (unsigned long long)std::max<int64_t>(64, N / 16);
+    record(h, 0);
+    int attempt = 0;
+    for (; attempt < 2; ++attempt) {
+        if ((r = grow(h, h->rg_pairs, 2 * sizeof(uint64_t) * (size_t)cap)) != CTWS_OK) return r;
+        if ((r = grow(h, h->rg_w, sizeof(uint64_t) * (size_t)cap)) != CTWS_OK) return r;
+        if ((r = grow(h, h->rg_nodes, sizeof(uint64_t) * (size_t)ncap)) != CTWS_OK) return r;
+        a.pairs = (uint64_t*)h->rg_pairs.p;
+        a.weights = (uint64_t*)h->rg_w.p;
+        a.nodes = (uint64_t*)h->rg_nodes.p;
+        a.cap = cap;
+        a.ncap = ncap;
+        HIPCHK(hipMemsetAsync(cnt, 0, 17 * sizeof(uint64_t), h->stream));
+        k_rag_pairs<<<g, 256, 0, h->stream>>>(a);
+        LAUNCHCHK();
+        HIPCHK(hipMemcpyAsync(emitted, cnt, sizeof(emitted), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (emitted[0] <= cap && emitted[16] <= ncap) break;
+        if (attempt == 1) {
+            h->err = "rag block: the emit counts changed between two passes over the same labels";
+            return CTWS_EHIP;
+        }
+        cap = std::max(cap, emitted[0]);
+        ncap = std::max(ncap, emitted[16]);
+    }
+    record(h, 1);
+    // nodes: the sorted unique of the emitted ids = np.unique of the block (without 0 under
+    // ignore_label: the kernel emits no 0 then)
+    int64_t nt = 0;
+    if ((r = rag_table(h, (const uint64_t*)h->rg_nodes.p, (int64_t)emitted[16], &nt)) != CTWS_OK) return r;
+    const uint64_t* tab = (const uint64_t*)h->rg_tab.p;
+    record(h, 7);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    rag_time(h, "rag_pairs", 0, 1);
+    rag_time(h, "rag_nodes", 1, 7);
+    add_timing(h, "rag_pair_passes", (float)(attempt + 1));  // (counts, as the flood's rounds)
+    add_timing(h, "rag_emits", (float)emitted[0]);
+    add_timing(h, "rag_node_emits", (float)emitted[16]);
+    int64_t m = 0;
+    if ((r = pairs_tail(h, (const uint64_t*)h->rg_pairs.p, (const uint64_t*)h->rg_w.p, (int64_t)emitted[0], tab, nt,
+                        &m)) != CTWS_OK)
+        return r;
+    *n_nodes = nt;
+    *n_edges = m;
+    if (*n_nodes > cap_nodes || m > cap_edges) {
+        h->err = "rag block: output capacity too small";
+        return CTWS_EINVAL;
+    }
+    if (*n_nodes)
+        HIPCHK(hipMemcpyAsync(nodes, tab, sizeof(uint64_t) * (size_t)*n_nodes,
+                              dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+    return pairs_out(h, m, dev ? 1 : 0, edges, counts);
+}
+}  // namespace
+}  // extern "C++"
+
+int ctws_unique_pairs_u64(ctws_handle* h, const uint64_t* pairs, const uint64_t* weights, int64_t n, int on_device,
+                          uint64_t* out, uint64_t* counts, int64_t cap, int64_t* n_unique) {
+    if (!h || (!pairs && n > 0) || n < 0 || !n_unique || cap < 0 || (!out && cap > 0)) return CTWS_EINVAL;
+    h->err.clear();
+    h->timings.clear();
+    HIPCHK(hipSetDevice(h->device));
+    *n_unique = 0;
+    if (n == 0) return CTWS_OK;
+    if (n >= (1ll << 30)) {
+        h->err = "unique pairs: 2^30 or more pairs in one call";
+        return CTWS_EUNSUPPORTED;
+    }
+    int r;
+    if (!on_device) {
+        if ((r = grow(h, h->rg_pairs, 2 * sizeof(uint64_t) * (size_t)n)) != CTWS_OK) return r;
+        HIPCHK(hipMemcpyAsync(h->rg_pairs.p, pairs, 2 * sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+        pairs = (const uint64_t*)h->rg_pairs.p;
+        if (weights) {
+            if ((r = grow(h, h->rg_lab, sizeof(uint64_t) * (size_t)n)) != CTWS_OK) return r;
+            HIPCHK(hipMemcpyAsync(h->rg_lab.p, weights, sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+            weights = (const uint64_t*)h->rg_lab.p;
+        }
+    }
+    // ids -> ranks: the distinct endpoint values
+    int64_t nt = 0;
+    if ((r = rag_table(h, pairs, 2 * n, &nt)) != CTWS_OK) return r;
+    int64_t m = 0;
+    if ((r = pairs_tail(h, pairs, weights, n, (const uint64_t*)h->rg_tab.p, nt, &m)) != CTWS_OK) return r;
+    *n_unique = m;
+    if (m > cap) {
+        h->err = "ctws_unique_pairs_u64: output capacity too small";
+        return CTWS_EINVAL;
+    }
+    return pairs_out(h, m, on_device, out, counts);
+}
+
+int ctws_rag_block(ctws_handle* h, const uint64_t* labels, int64_t nz, int64_t ny, int64_t nx, int ignore_label,
+                   uint64_t* nodes, int64_t cap_nodes, int64_t* n_nodes, uint64_t* edges, uint64_t* counts,
+                   int64_t cap_edges, int64_t* n_edges) {
+    return rag_block(h, labels, nz, ny, nx, ignore_label, nodes, cap_nodes, n_nodes, edges, counts, cap_edges, n_edges,
+                     false);
+}
+
+int ctws_rag_block_device(ctws_handle* h, const uint64_t* labels, int64_t nz, int64_t ny, int64_t nx, int ignore_label,
+                          uint64_t* nodes, int64_t cap_nodes, int64_t* n_nodes, uint64_t* edges, uint64_t* counts,
+                          int64_t cap_edges, int64_t* n_edges) {
+    return rag_block(h, labels, nz, ny, nx, ignore_label, nodes, cap_nodes, n_nodes, edges, counts, cap_edges, n_edges,
+                     true);
 }
 
 

@@ -297,6 +297,27 @@ __global__ void k_u64_lookup(uint64_t*, int64_t, const uint64_t*, const uint64_t
 hipError_t u64_sort(void* tmp, size_t& bytes, const uint64_t* in, uint64_t* out, int64_t n, hipStream_t stream);
 hipError_t u64_runs(void* tmp, size_t& bytes, const uint64_t* sorted, uint64_t* uniq, uint64_t* counts,
                     uint64_t* n_runs, int64_t n, hipStream_t stream);
+// k_rag.hip (GraphWorkflow: face-adjacent id pairs of a block, sorted unique pairs with summed weights)
+struct RagArgs {
+    const uint64_t* lab;        // the block's labels, (nz, ny, nx)
+    uint32_t nz, ny, nx;        // nz * ny * nx < 2^31
+    int ignore;                 // ignore_label: pairs with a 0 are dropped
+    uint64_t* pairs;            // out: (min, max) per emit, cap x 2
+    uint64_t* weights;          // out: the emit's run length
+    unsigned long long cap;     // emits at positions >= cap are counted, not written
+    unsigned long long* count;  // the append counter
+    uint64_t* nodes;            // out: the ids of the voxels whose three upper neighbours differ
+    unsigned long long ncap;    // as cap, for nodes
+    unsigned long long* ncount;
+};
+__global__ void k_rag_pairs(RagArgs);
+__global__ void k_pair_keys(const uint64_t*, int64_t, const uint64_t*, int64_t, int, uint64_t*, unsigned long long*);
+__global__ void k_pair_ones(uint64_t*, int64_t);
+__global__ void k_pair_unpack(const uint64_t*, int64_t, const uint64_t*, int, uint64_t*);
+hipError_t pair_sort(void* tmp, size_t& bytes, const uint64_t* keys_in, uint64_t* keys_out, const uint64_t* w_in,
+                     uint64_t* w_out, int64_t n, int end_bit, hipStream_t stream);
+hipError_t pair_reduce(void* tmp, size_t& bytes, const uint64_t* keys, uint64_t* uniq, const uint64_t* w,
+                       uint64_t* sums, uint64_t* n_runs, int64_t n, hipStream_t stream);
 
 // k_threshcc.hip (ThresholdedComponents: BlockComponents)
 struct TcParams {

@@ -64,6 +64,12 @@ def lib():
             L.ctws_set_discard_u64.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
             L.ctws_size_filter_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
             L.ctws_size_filter_blocks_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+            L.ctws_unique_pairs_u64.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p,
+                                                C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+            for fn in ('ctws_rag_block', 'ctws_rag_block_device'):
+                getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int,
+                                           C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p,
+                                           C.c_int64, C.POINTER(C.c_int64)]
             L.ctws_threshold_components.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                                     C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p,
                                                     C.POINTER(C.c_int64)]
@@ -88,7 +94,7 @@ EXPORTED_SYMBOLS = ('ctws_abi_version', 'ctws_open', 'ctws_close', 'ctws_last_er
                     'ctws_debug_set_stop', 'ctws_debug_read', 'ctws_debug_sqrt_int', 'ctws_ws_from_seeds', 'ctws_ws_from_seeds_device',
                     'ctws_eval_begin', 'ctws_eval_add', 'ctws_eval_end', 'ctws_threshold_components',
                     'ctws_threshold_components_ex', 'ctws_ufd_find', 'ctws_set_discard_u64', 'ctws_size_filter_blocks',
-                    'ctws_size_filter_blocks_device')
+                    'ctws_size_filter_blocks_device', 'ctws_unique_pairs_u64', 'ctws_rag_block', 'ctws_rag_block_device')
 
 
 def ufd_find(n_labels, pairs):
@@ -570,5 +576,89 @@ class Handle:
         self._check(lib().ctws_lookup_u64(self._h, labels.data_ptr(), labels.numel(), 1, kd.data_ptr(), vd.data_ptr(),
                                           kd.numel(), C.byref(miss)), 'ctws_lookup_u64')
         return int(miss.value)
+
+    # ---- GraphWorkflow kernels ------------------------------------------------------------
+    def unique_pairs_u64_raw(self, pairs, weights, cap):
+        """One ctws_unique_pairs_u64 call with an output of `cap` rows:
+        (return code, n_unique, out (cap, 2), counts (cap,))."""
+        pairs = np.ascontiguousarray(pairs, dtype=np.uint64).reshape(-1, 2)
+        wp = None
+        if weights is not None:
+            weights = np.ascontiguousarray(weights, dtype=np.uint64).ravel()
+            assert weights.size == len(pairs), (weights.size, len(pairs))
+            wp = weights.ctypes.data if weights.size else None
+        out = np.empty((cap, 2), dtype=np.uint64)
+        cnt = np.empty(cap, dtype=np.uint64)
+        n = C.c_int64(0)
+        ret = lib().ctws_unique_pairs_u64(self._h, pairs.ctypes.data if len(pairs) else None, wp, len(pairs), 0,
+                                          out.ctypes.data if cap else None, cnt.ctypes.data if cap else None,
+                                          cap, C.byref(n))
+        return ret, int(n.value), out, cnt
+
+    def unique_pairs_u64(self, pairs, weights=None):
+        """np.unique(pairs, axis=0) of an (n, 2) uint64 array on the GPU with the summed weights of
+        equal rows (weights None: their number): (unique rows (m, 2), sums (m,)), both uint64.  The
+        edge merge of MergeSubGraphs.  A call that hits the capacity is repeated once with the
+        returned size."""
+        n_pairs = int(np.asarray(pairs).size // 2)
+        ret, m, out, cnt = self.unique_pairs_u64_raw(pairs, weights, min(n_pairs, 4096))
+        if ret == -1 and m > len(cnt):
+            ret, m, out, cnt = self.unique_pairs_u64_raw(pairs, weights, m)
+        self._check(ret, 'ctws_unique_pairs_u64')
+        return out[:m], cnt[:m]
+
+    # first capacities of rag_block (nodes, edges): a 64 x 512 x 512 block of fragments has ~2,700
+    # nodes and ~16,500 edges, and a call that does not fit computes everything again
+    RAG_CAPS = (1 << 16, 1 << 18)
+
+    def rag_block_raw(self, labels, ignore_label, cap_nodes, cap_edges):
+        """One ctws_rag_block call with outputs of the given capacities: (return code, n_nodes,
+        n_edges, nodes (cap_nodes,), edges (cap_edges, 2), counts (cap_edges,))."""
+        labels = np.ascontiguousarray(labels, dtype=np.uint64)
+        assert labels.ndim == 3 and labels.size, labels.shape
+        nodes = np.empty(cap_nodes, dtype=np.uint64)
+        edges = np.empty((cap_edges, 2), dtype=np.uint64)
+        counts = np.empty(cap_edges, dtype=np.uint64)
+        nn, ne = C.c_int64(0), C.c_int64(0)
+        ret = lib().ctws_rag_block(self._h, labels.ctypes.data, *labels.shape, int(bool(ignore_label)),
+                                   nodes.ctypes.data if cap_nodes else None, cap_nodes, C.byref(nn),
+                                   edges.ctypes.data if cap_edges else None,
+                                   counts.ctypes.data if cap_edges else None, cap_edges, C.byref(ne))
+        return ret, int(nn.value), int(ne.value), nodes, edges, counts
+
+    def rag_block(self, labels, ignore_label=True):
+        """The region adjacency graph of a 3-D uint64 label block (the extended box of
+        InitialSubGraphs): (nodes (n,), edges (m, 2), counts (m,)), uint64.  nodes = np.unique
+        (without 0 under ignore_label); edges = the sorted (min, max) id pairs of face-adjacent
+        voxels with different ids (none with a 0 under ignore_label); counts = the voxel pairs per
+        edge.  A call that hits a capacity is repeated once with the returned sizes."""
+        cn, ce = self.RAG_CAPS
+        ret, nn, ne, nodes, edges, counts = self.rag_block_raw(labels, ignore_label, cn, ce)
+        if ret == -1 and (nn > cn or ne > ce):
+            ret, nn, ne, nodes, edges, counts = self.rag_block_raw(labels, ignore_label, max(nn, 1), max(ne, 1))
+        self._check(ret, 'ctws_rag_block')
+        return nodes[:nn], edges[:ne], counts[:ne]
+
+    def rag_block_device(self, labels, ignore_label=True):
+        """rag_block on a uint64 / int64 torch tensor on this GPU; nodes, edges and counts come
+        back as int64 tensors (uint64 bits) on the same device: only the two sizes cross PCIe."""
+        import torch
+        assert labels.is_cuda and labels.is_contiguous() and labels.element_size() == 8 and labels.dim() == 3
+        assert labels.numel() > 0
+        torch.cuda.current_stream(labels.device).synchronize()
+        nn, ne = C.c_int64(0), C.c_int64(0)
+        cn, ce = self.RAG_CAPS
+        for _ in range(2):
+            nodes = torch.empty(cn, dtype=torch.int64, device=labels.device)
+            edges = torch.empty((ce, 2), dtype=torch.int64, device=labels.device)
+            counts = torch.empty(ce, dtype=torch.int64, device=labels.device)
+            ret = lib().ctws_rag_block_device(self._h, labels.data_ptr(), *labels.shape, int(bool(ignore_label)),
+                                              nodes.data_ptr(), cn, C.byref(nn), edges.data_ptr(),
+                                              counts.data_ptr(), ce, C.byref(ne))
+            if not (ret == -1 and (nn.value > cn or ne.value > ce)):
+                break
+            cn, ce = max(nn.value, 1), max(ne.value, 1)
+        self._check(ret, 'ctws_rag_block_device')
+        return nodes[:nn.value], edges[:ne.value], counts[:ne.value]
 
     # ---- multi-GPU label-count exchange (RCCL) ------------------------------------------

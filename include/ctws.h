@@ -262,6 +262,37 @@ int ctws_lookup_u64(ctws_handle* h, uint64_t* labels, int64_t n, int on_device, 
                     const uint64_t* values, int64_t n_table, int64_t* n_missing);
 
 /*
+ * GraphWorkflow (graph/graph_workflow.py:9-72): the region adjacency graph of the fragments.
+ *
+ * ctws_rag_block / _device: the graph of one block of uint64 labels, shape (nz, ny, nx), C order
+ *   -- the extended box [block.begin, min(block.end + 1, shape)) of InitialSubGraphs
+ *   (initial_sub_graphs.py:106-120, `ndist.computeMergeableRegionGraph(..., increaseRoi=True)`).
+ *     nodes   the sorted unique labels (np.unique), without 0 when ignore_label is set
+ *     edges   the sorted set of (min(u, v), max(u, v)) over all face-adjacent voxel pairs of the
+ *             block with u != v -- and u != 0, v != 0 when ignore_label is set -- as m x 2
+ *             (`nrag.gridRag(seg).uvIds()`, test/graph/test_graph.py:63-126)
+ *     counts  per edge the number of such voxel pairs; may be NULL
+ *   *n_nodes and *n_edges are always set; CTWS_EINVAL when cap_nodes or cap_edges is too small
+ *   (nothing written: retry with those sizes).  Every uint64 value is a legal id.  Fewer than
+ *   2^31 voxels per block.  Host pointers are staged through HBM; _device takes device pointers
+ *   on the handle's GPU for labels, nodes, edges and counts.
+ * ctws_unique_pairs_u64: the lexicographically sorted unique rows of pairs (n x 2) into out
+ *   (cap x 2) with the sum of their weights (weights == NULL: 1 each) into counts (cap entries, or
+ *   NULL) -- the edge part of `ndist.mergeSubgraphs` (merge_sub_graphs.py:133-158) on the
+ *   concatenated edge tables of the children.  *n_unique is always set; CTWS_EINVAL when cap is
+ *   too small.  on_device as for ctws_unique_u64.  Fewer than 2^30 pairs and 2^32 distinct
+ *   values per call (CTWS_EUNSUPPORTED otherwise).
+ */
+int ctws_unique_pairs_u64(ctws_handle* h, const uint64_t* pairs, const uint64_t* weights, int64_t n, int on_device,
+                          uint64_t* out, uint64_t* counts, int64_t cap, int64_t* n_unique);
+int ctws_rag_block(ctws_handle* h, const uint64_t* labels, int64_t nz, int64_t ny, int64_t nx, int ignore_label,
+                   uint64_t* nodes, int64_t cap_nodes, int64_t* n_nodes, uint64_t* edges, uint64_t* counts,
+                   int64_t cap_edges, int64_t* n_edges);
+int ctws_rag_block_device(ctws_handle* h, const uint64_t* labels, int64_t nz, int64_t ny, int64_t nx,
+                          int ignore_label, uint64_t* nodes, int64_t cap_nodes, int64_t* n_nodes, uint64_t* edges,
+                          uint64_t* counts, int64_t cap_edges, int64_t* n_edges);
+
+/*
  * ThresholdedComponentsWorkflow, BlockComponents (thresholded_components/block_components.py:
  * 143-230: `_cc_block` / `_cc_block_with_mask`, threshold + skimage.morphology.label) on the GPU.
  *
