@@ -130,6 +130,9 @@ struct ctws_handle {
     // endpoint table, the emitted node ids, pairs and weights, keys (then the unique keys), sorted keys and
     // weights, summed weights, unpacked edges, sort / reduce temp, counters (append, runs, missing)
     DevBuf rg_lab, rg_tab, rg_nodes, rg_pairs, rg_w, rg_keys, rg_skeys, rg_sw, rg_sum, rg_out, rg_tmp, rg_red;
+    // EdgeFeaturesWorkflow (k_edgefeat.hip): host-pointer staging of labels / data / nodes / edges / rows,
+    // the edge keys, the sample keys and their sorted copy, sort temp, counters (append, missing, bad edges)
+    DevBuf ef_lab, ef_data, ef_nodes, ef_edges, ef_out, ef_ekeys, ef_keys, ef_skeys, ef_tmp, ef_red;
     int64_t sf_n = 0;
     uint64_t sf_lo = 1, sf_hi = 0;
     bool sf_has_bits = false;
@@ -2545,7 +2548,8 @@ void ctws_close(ctws_handle* h) {
                     w.fplat, w.plev, w.fseed, h->tc_P.p, h->tc_bits.p, h->tc_cnt.p, h->tc_offs.p, h->tc_woff.p,
                     h->tc_red.p, h->tc_in.p, h->tc_mask.p, h->tc_out.p, h->tc_raw.p, h->tc_tmp.p, h->tc_taps.p,
                     h->rg_lab.p, h->rg_tab.p, h->rg_nodes.p, h->rg_pairs.p, h->rg_w.p, h->rg_keys.p, h->rg_skeys.p, h->rg_sw.p,
-                    h->rg_sum.p, h->rg_out.p, h->rg_tmp.p, h->rg_red.p};
+                    h->rg_sum.p, h->rg_out.p, h->rg_tmp.p, h->rg_red.p, h->ef_lab.p, h->ef_data.p, h->ef_nodes.p,
+                    h->ef_edges.p, h->ef_out.p, h->ef_ekeys.p, h->ef_keys.p, h->ef_skeys.p, h->ef_tmp.p, h->ef_red.p};
     for (void* p : ptrs)
         if (p) hipFree(p);
     for (auto e : h->events) hipEventDestroy(e);
@@ -3441,6 +3445,174 @@ int ctws_rag_block_device(ctws_handle* h, const uint64_t* labels, int64_t nz, in
                      true);
 }
 
+
+// ---- EdgeFeaturesWorkflow: boundary-map statistics per edge (k_edgefeat.hip) ----------------
+extern "C++" {
+namespace {
+int edge_features_block(ctws_handle* h, const uint64_t* labels, const void* data, int data_dtype, int64_t nz,
+                        int64_t ny, int64_t nx, int64_t cz, int64_t cy, int64_t cx, int ignore_label,
+                        const uint64_t* nodes, int64_t n_nodes, const uint64_t* edges, int64_t n_edges, double* out,
+                        int64_t* n_missing, bool dev) {
+    if (!h) return CTWS_EINVAL;
+    h->err.clear();
+    h->timings.clear();
+    if (n_missing) *n_missing = 0;
+    if (!labels || !data || nz <= 0 || ny <= 0 || nx <= 0 || cz <= 0 || cy <= 0 || cx <= 0 || cz > nz || cy > ny ||
+        cx > nx || n_nodes < 0 || n_edges < 0 || (n_edges > 0 && (!nodes || !edges || !out || n_nodes == 0))) {
+        h->err = "edge features: bad arguments (3-D boxes with 0 < core <= extended, tables for n_edges > 0)";
+        return CTWS_EINVAL;
+    }
+    if (data_dtype != CTWS_F32 && data_dtype != CTWS_U8) {
+        h->err = "edge features: the boundary map is float32 or uint8";
+        return CTWS_EUNSUPPORTED;
+    }
+    HIPCHK(hipSetDevice(h->device));
+    if (n_edges == 0) return CTWS_OK;  // nothing to accumulate into: no launch
+    constexpr int64_t kMax = 1ll << 31;
+    if (nz >= kMax || ny >= kMax || nx >= kMax || nz * ny >= kMax || nz * ny * nx >= kMax) {
+        h->err = "edge features: 2^31 or more voxels in one block (the sample kernel indexes a block with 32 bits)";
+        return CTWS_EUNSUPPORTED;
+    }
+    if (n_nodes >= (1ll << 32) || n_edges >= (1ll << 32)) {
+        h->err = "edge features: 2^32 or more nodes or edges in one block";
+        return CTWS_EUNSUPPORTED;
+    }
+    const int64_t N = nz * ny * nx;
+    const size_t es = data_dtype == CTWS_U8 ? 1 : 4;
+    int r;
+    const uint64_t *dl = labels, *dn = nodes, *de = edges;
+    const void* dd = data;
+    double* dout = out;
+    const size_t out_bytes = 10 * sizeof(double) * (size_t)n_edges;
+    if (!dev) {
+        if ((r = grow(h, h->ef_lab, sizeof(uint64_t) * (size_t)N)) != CTWS_OK) return r;
+        if ((r = grow(h, h->ef_data, es * (size_t)N)) != CTWS_OK) return r;
+        if ((r = grow(h, h->ef_nodes, sizeof(uint64_t) * (size_t)n_nodes)) != CTWS_OK) return r;
+        if ((r = grow(h, h->ef_edges, 2 * sizeof(uint64_t) * (size_t)n_edges)) != CTWS_OK) return r;
+        if ((r = grow(h, h->ef_out, out_bytes)) != CTWS_OK) return r;
+        HIPCHK(copy_pieces(h->ef_lab.p, labels, sizeof(uint64_t) * (size_t)N, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(copy_pieces(h->ef_data.p, data, es * (size_t)N, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(h->ef_nodes.p, nodes, sizeof(uint64_t) * (size_t)n_nodes, hipMemcpyHostToDevice,
+                              h->stream));
+        HIPCHK(hipMemcpyAsync(h->ef_edges.p, edges, 2 * sizeof(uint64_t) * (size_t)n_edges, hipMemcpyHostToDevice,
+                              h->stream));
+        dl = (const uint64_t*)h->ef_lab.p;
+        dd = h->ef_data.p;
+        dn = (const uint64_t*)h->ef_nodes.p;
+        de = (const uint64_t*)h->ef_edges.p;
+        dout = (double*)h->ef_out.p;
+    }
+    int b = 1;  // bits per rank
+    while ((1ll << b) < n_nodes) ++b;
+    int eb = 1;  // bits per edge index
+    while ((1ll << eb) < n_edges) ++eb;
+    // counters: [0] the append counter on a 128-B line of its own, [16] missing pairs, [17] bad edges
+    if ((r = grow(h, h->ef_red, 32 * sizeof(uint64_t))) != CTWS_OK) return r;
+    if ((r = grow(h, h->ef_ekeys, sizeof(uint64_t) * (size_t)n_edges)) != CTWS_OK) return r;
+    unsigned long long* cnt = (unsigned long long*)h->ef_red.p;
+    HIPCHK(hipMemsetAsync(cnt, 0, 32 * sizeof(uint64_t), h->stream));
+    record(h, 0);
+    const unsigned ge = (unsigned)std::min<int64_t>((n_edges + 255) / 256, 8192);
+    k_ef_edge_keys<<<ge, 256, 0, h->stream>>>(de, n_edges, dn, n_nodes, b, (uint64_t*)h->ef_ekeys.p, cnt + 17);
+    LAUNCHCHK();
+    record(h, 1);
+    EfArgs a;
+    a.lab = dl;
+    a.data = dd;
+    a.nz = (uint32_t)nz;
+    a.ny = (uint32_t)ny;
+    a.nx = (uint32_t)nx;
+    a.cz = (uint32_t)cz;
+    a.cy = (uint32_t)cy;
+    a.cx = (uint32_t)cx;
+    a.ignore = ignore_label ? 1 : 0;
+    a.tab = dn;
+    a.nt = (uint32_t)n_nodes;
+    a.b = b;
+    a.ekeys = (const uint64_t*)h->ef_ekeys.p;
+    a.ne = (uint32_t)n_edges;
+    a.count = cnt;
+    a.missing = cnt + 16;
+    const int64_t rows = cz * cy;
+    // the grid of k_rag_pairs: four workgroups per CU, every wave ends with an append of its own
+    const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>((rows + 3) / 4, 1024));
+    // first capacity: half a key per voxel (a block of fragments emits ~0.38), a function of the
+    // block alone; the pass is repeated at the counted size when it did not fit
+    unsigned long long cap = (unsigned long long)std::max<int64_t>(64, N / 2);
+    unsigned long long res[18] = {0};
+    int attempt = 0;
+    for (; attempt < 2; ++attempt) {
+        if ((r = grow(h, h->ef_keys, sizeof(uint64_t) * (size_t)cap)) != CTWS_OK) return r;
+        a.keys = (uint64_t*)h->ef_keys.p;
+        a.cap = cap;
+        HIPCHK(hipMemsetAsync(cnt, 0, 17 * sizeof(uint64_t), h->stream));  // (not the bad-edge count)
+        if (data_dtype == CTWS_U8) k_ef_samples<uint8_t><<<g, 256, 0, h->stream>>>(a);
+        else k_ef_samples<float><<<g, 256, 0, h->stream>>>(a);
+        LAUNCHCHK();
+        HIPCHK(hipMemcpyAsync(res, cnt, sizeof(res), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (res[17]) {
+            h->err = "edge features: " + std::to_string(res[17]) +
+                     " edges have an endpoint missing from the nodes or are not sorted and unique";
+            return CTWS_EINVAL;
+        }
+        if (res[0] <= cap) break;
+        if (attempt == 1) {
+            h->err = "edge features: the sample count changed between two passes over the same block";
+            return CTWS_EHIP;
+        }
+        cap = res[0];
+    }
+    record(h, 2);
+    const int64_t n = (int64_t)res[0];
+    if (n >= kMax) {
+        h->err = "edge features: 2^31 or more samples in one block";
+        return CTWS_EUNSUPPORTED;
+    }
+    if (n_missing) *n_missing = (int64_t)res[16];
+    const uint64_t* sorted = (const uint64_t*)h->ef_keys.p;
+    if (n) {
+        size_t tb = 0;
+        HIPCHK(ef_sort(nullptr, tb, nullptr, nullptr, n, 32 + eb, h->stream));
+        if ((r = grow(h, h->ef_skeys, sizeof(uint64_t) * (size_t)n)) != CTWS_OK) return r;
+        if ((r = grow(h, h->ef_tmp, tb)) != CTWS_OK) return r;
+        HIPCHK(ef_sort(h->ef_tmp.p, tb, (const uint64_t*)h->ef_keys.p, (uint64_t*)h->ef_skeys.p, n, 32 + eb,
+                       h->stream));
+        sorted = (const uint64_t*)h->ef_skeys.p;
+    }
+    record(h, 3);
+    // one wave per edge, four per workgroup
+    k_ef_stats<<<(unsigned)((n_edges + 3) / 4), 256, 0, h->stream>>>(sorted, (uint32_t)n, (uint32_t)n_edges, dout);
+    LAUNCHCHK();
+    record(h, 4);
+    if (!dev) HIPCHK(hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    rag_time(h, "ef_edge_keys", 0, 1);
+    rag_time(h, "ef_samples", 1, 2);
+    rag_time(h, "ef_sort", 2, 3);
+    rag_time(h, "ef_stats", 3, 4);
+    add_timing(h, "ef_sample_passes", (float)(attempt + 1));
+    add_timing(h, "ef_keys", (float)n);
+    return CTWS_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int ctws_edge_features_block(ctws_handle* h, const uint64_t* labels, const void* data, int data_dtype, int64_t nz,
+                             int64_t ny, int64_t nx, int64_t cz, int64_t cy, int64_t cx, int ignore_label,
+                             const uint64_t* nodes, int64_t n_nodes, const uint64_t* edges, int64_t n_edges,
+                             double* out, int64_t* n_missing) {
+    return edge_features_block(h, labels, data, data_dtype, nz, ny, nx, cz, cy, cx, ignore_label, nodes, n_nodes,
+                               edges, n_edges, out, n_missing, false);
+}
+
+int ctws_edge_features_block_device(ctws_handle* h, const uint64_t* labels, const void* data, int data_dtype,
+                                    int64_t nz, int64_t ny, int64_t nx, int64_t cz, int64_t cy, int64_t cx,
+                                    int ignore_label, const uint64_t* nodes, int64_t n_nodes, const uint64_t* edges,
+                                    int64_t n_edges, double* out, int64_t* n_missing) {
+    return edge_features_block(h, labels, data, data_dtype, nz, ny, nx, cz, cy, cx, ignore_label, nodes, n_nodes,
+                               edges, n_edges, out, n_missing, true);
+}
 
 // ---- ThresholdedComponentsWorkflow: BlockComponents (k_threshcc.hip) -----------------------
 extern "C++" {

@@ -318,6 +318,29 @@ hipError_t pair_sort(void* tmp, size_t& bytes, const uint64_t* keys_in, uint64_t
                      uint64_t* w_out, int64_t n, int end_bit, hipStream_t stream);
 hipError_t pair_reduce(void* tmp, size_t& bytes, const uint64_t* keys, uint64_t* uniq, const uint64_t* w,
                        uint64_t* sums, uint64_t* n_runs, int64_t n, hipStream_t stream);
+// k_edgefeat.hip (EdgeFeaturesWorkflow: the boundary-map statistics of a block's edges)
+struct EfArgs {
+    const uint64_t* lab;          // the block's labels, (nz, ny, nx): the extended box
+    const void* data;             // the boundary map on the same box, float32 or uint8
+    uint32_t nz, ny, nx;          // nz * ny * nx < 2^31
+    uint32_t cz, cy, cx;          // the core extent: a pair belongs to the block of its lower voxel
+    int ignore;                   // ignore_label: pairs with a 0 are dropped
+    const uint64_t* tab;          // the sub-graph's nodes, ascending
+    uint32_t nt;
+    int b;                        // bits per rank
+    const uint64_t* ekeys;        // the sub-graph's edges as rank(u) << b | rank(v), ascending
+    uint32_t ne;
+    uint64_t* keys;               // out: edge << 32 | ordered(value), two per owned pair
+    unsigned long long cap;       // keys at positions >= cap are counted, not written
+    unsigned long long* count;    // the append counter
+    unsigned long long* missing;  // owned pairs whose edge is not in the table
+};
+__global__ void k_ef_edge_keys(const uint64_t*, int64_t, const uint64_t*, int64_t, int, uint64_t*, unsigned long long*);
+template <class T>
+__global__ void k_ef_samples(EfArgs);
+__global__ void k_ef_stats(const uint64_t*, uint32_t, uint32_t, double*);
+hipError_t ef_sort(void* tmp, size_t& bytes, const uint64_t* keys_in, uint64_t* keys_out, int64_t n, int end_bit,
+                   hipStream_t stream);
 
 // k_threshcc.hip (ThresholdedComponents: BlockComponents)
 struct TcParams {

@@ -70,6 +70,9 @@ def lib():
                 getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int,
                                            C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p,
                                            C.c_int64, C.POINTER(C.c_int64)]
+            for fn in ('ctws_edge_features_block', 'ctws_edge_features_block_device'):
+                getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_int64] * 6 + [
+                    C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]
             L.ctws_threshold_components.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                                     C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p,
                                                     C.POINTER(C.c_int64)]
@@ -94,7 +97,8 @@ EXPORTED_SYMBOLS = ('ctws_abi_version', 'ctws_open', 'ctws_close', 'ctws_last_er
                     'ctws_debug_set_stop', 'ctws_debug_read', 'ctws_debug_sqrt_int', 'ctws_ws_from_seeds', 'ctws_ws_from_seeds_device',
                     'ctws_eval_begin', 'ctws_eval_add', 'ctws_eval_end', 'ctws_threshold_components',
                     'ctws_threshold_components_ex', 'ctws_ufd_find', 'ctws_set_discard_u64', 'ctws_size_filter_blocks',
-                    'ctws_size_filter_blocks_device', 'ctws_unique_pairs_u64', 'ctws_rag_block', 'ctws_rag_block_device')
+                    'ctws_size_filter_blocks_device', 'ctws_unique_pairs_u64', 'ctws_rag_block', 'ctws_rag_block_device',
+                    'ctws_edge_features_block', 'ctws_edge_features_block_device')
 
 
 def ufd_find(n_labels, pairs):
@@ -660,5 +664,66 @@ class Handle:
             cn, ce = max(nn.value, 1), max(ne.value, 1)
         self._check(ret, 'ctws_rag_block_device')
         return nodes[:nn.value], edges[:ne.value], counts[:ne.value]
+
+    # ---- EdgeFeaturesWorkflow kernels ------------------------------------------------------
+    def edge_features_block(self, labels, data, nodes, edges, ignore_label=True, core_shape=None):
+        """The boundary-map features of the edges of one block (include/ctws.h,
+        ctws_edge_features_block): labels (uint64) and data (float32, or uint8 taken as v / 255) on
+        the block's extended box, nodes / edges its sub-graph (Handle.rag_block), core_shape the
+        extent of the block itself (None: the whole box).  -> (features (m, 10) float64: mean,
+        variance, min, q10, q25, q50, q75, q90, max, count per edge; n_missing = the owned voxel
+        pairs whose edge is not in `edges`).  No edges: an empty table without a launch."""
+        labels = np.ascontiguousarray(labels, dtype=np.uint64)
+        data = np.ascontiguousarray(data)
+        nodes = np.ascontiguousarray(nodes, dtype=np.uint64).ravel()
+        edges = np.ascontiguousarray(edges, dtype=np.uint64).reshape(-1, 2)
+        if labels.ndim != 3 or data.shape != labels.shape or not labels.size:
+            raise ValueError("edge features: labels and data are 3-D and of one shape, not %s and %s"
+                             % (labels.shape, data.shape))
+        if data.dtype not in (np.dtype('float32'), np.dtype('uint8')):
+            raise TypeError("edge features: the boundary map is float32 or uint8, not %s" % data.dtype)
+        core = self._core_shape(core_shape, labels.shape)
+        out = np.zeros((len(edges), 10), dtype=np.float64)
+        if len(edges) == 0:
+            return out, 0
+        miss = C.c_int64(0)
+        self._check(lib().ctws_edge_features_block(self._h, labels.ctypes.data, data.ctypes.data, dtype_code(data.dtype),
+                                                   *labels.shape, *core, int(bool(ignore_label)), nodes.ctypes.data,
+                                                   len(nodes), edges.ctypes.data, len(edges), out.ctypes.data,
+                                                   C.byref(miss)), 'ctws_edge_features_block')
+        return out, int(miss.value)
+
+    @staticmethod
+    def _core_shape(core_shape, shape):
+        core = tuple(int(c) for c in (shape if core_shape is None else core_shape))
+        if len(core) != 3 or any(c <= 0 or c > s for c, s in zip(core, shape)):
+            raise ValueError("edge features: core shape %s does not fit the box %s" % (core, tuple(shape)))
+        return core
+
+    def edge_features_block_device(self, labels, data, nodes, edges, ignore_label=True, core_shape=None):
+        """edge_features_block on torch tensors on this GPU: labels, nodes and edges uint64 / int64,
+        data float32 or uint8; the features come back as a float64 tensor on the same device, only
+        n_missing crosses PCIe."""
+        import torch
+        for t in (labels, data, nodes, edges):
+            assert t.is_cuda and t.is_contiguous()
+        assert labels.dim() == 3 and labels.numel() > 0 and data.shape == labels.shape
+        assert labels.element_size() == 8 and nodes.element_size() == 8 and edges.element_size() == 8
+        if data.dtype not in (torch.float32, torch.uint8):
+            raise TypeError("edge features: the boundary map is float32 or uint8, not %s" % data.dtype)
+        core = self._core_shape(core_shape, tuple(labels.shape))
+        m = edges.numel() // 2
+        out = torch.zeros((m, 10), dtype=torch.float64, device=labels.device)
+        if m == 0:
+            return out, 0
+        torch.cuda.current_stream(labels.device).synchronize()
+        miss = C.c_int64(0)
+        code = dtype_code(np.dtype('float32' if data.dtype == torch.float32 else 'uint8'))
+        self._check(lib().ctws_edge_features_block_device(self._h, labels.data_ptr(), data.data_ptr(), code,
+                                                          *labels.shape, *core, int(bool(ignore_label)),
+                                                          nodes.data_ptr(), nodes.numel(), edges.data_ptr(), m,
+                                                          out.data_ptr(), C.byref(miss)),
+                    'ctws_edge_features_block_device')
+        return out, int(miss.value)
 
     # ---- multi-GPU label-count exchange (RCCL) ------------------------------------------

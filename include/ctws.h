@@ -293,6 +293,44 @@ int ctws_rag_block_device(ctws_handle* h, const uint64_t* labels, int64_t nz, in
                           uint64_t* counts, int64_t cap_edges, int64_t* n_edges);
 
 /*
+ * EdgeFeaturesWorkflow (features/features_workflow.py:14-66), BlockEdgeFeatures: the boundary-map
+ * statistics of the edges of one block (block_edge_features.py:113-132,
+ * `ndist.extractBlockFeaturesFromBoundaryMaps_*`, restated: DESIGN.md section 3.5).
+ *
+ * ctws_edge_features_block / _device: labels (uint64) and data (data_dtype CTWS_F32 or CTWS_U8;
+ *   uint8 values are taken as float32(v) / float32(255)) on the block's extended box (nz, ny, nx),
+ *   C order; (cz, cy, cx) <= (nz, ny, nx) is the extent of the core box [block.begin, block.end).
+ *   nodes (n_nodes, ascending) and edges (n_edges x 2, sorted) are the block's sub-graph as
+ *   ctws_rag_block gives it, ignore_label its `ignoreLabel`.
+ *     pairs   every face-adjacent voxel pair (p, p + e_axis) with p in the core box, p + e_axis in
+ *             the extended box and different ids -- neither 0 when ignore_label is set.  A pair
+ *             wholly in the upper halo planes belongs to the neighbouring block: every pair of a
+ *             volume is owned by exactly one block.
+ *     samples each pair gives its edge both voxel values; the n = 2 * count samples of an edge are
+ *             taken as float64 and sorted ascending into s
+ *     out     n_edges x 10 float64, a row per edge in the order of edges:
+ *             [mean, variance, min, q10, q25, q50, q75, q90, max, count] with mean = sum(s) / n,
+ *             variance = sum((s - mean)^2) / n, quantile q = s[l] + (pos - l) (s[h] - s[l]) for
+ *             pos = q (n - 1), l = floor(pos), h = min(l + 1, n - 1), count = the pairs.  An edge
+ *             without an owned pair gets ten zeros.
+ *   *n_missing (may be NULL) = the owned pairs whose edge is not in the table, as ctws_lookup_u64
+ *   reports its misses; they contribute nothing.  n_edges == 0 returns at once (no launch, nothing
+ *   counted).  CTWS_EINVAL when an edge has an endpoint that is no node or the edges are not
+ *   sorted and unique.  Any finite value is legal, NaN is not supported.  The rows depend on the
+ *   inputs alone (no floating-point atomics: repeated calls agree bit for bit).  Fewer than 2^31
+ *   voxels and samples, 2^32 nodes and edges per block.  Host pointers are staged through HBM;
+ *   _device takes device pointers on the handle's GPU for labels, data, nodes, edges and out.
+ */
+int ctws_edge_features_block(ctws_handle* h, const uint64_t* labels, const void* data, int data_dtype, int64_t nz,
+                             int64_t ny, int64_t nx, int64_t cz, int64_t cy, int64_t cx, int ignore_label,
+                             const uint64_t* nodes, int64_t n_nodes, const uint64_t* edges, int64_t n_edges,
+                             double* out, int64_t* n_missing);
+int ctws_edge_features_block_device(ctws_handle* h, const uint64_t* labels, const void* data, int data_dtype,
+                                    int64_t nz, int64_t ny, int64_t nx, int64_t cz, int64_t cy, int64_t cx,
+                                    int ignore_label, const uint64_t* nodes, int64_t n_nodes, const uint64_t* edges,
+                                    int64_t n_edges, double* out, int64_t* n_missing);
+
+/*
  * ThresholdedComponentsWorkflow, BlockComponents (thresholded_components/block_components.py:
  * 143-230: `_cc_block` / `_cc_block_with_mask`, threshold + skimage.morphology.label) on the GPU.
  *
