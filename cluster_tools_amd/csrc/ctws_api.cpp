@@ -133,6 +133,9 @@ struct ctws_handle {
     // EdgeFeaturesWorkflow (k_edgefeat.hip): host-pointer staging of labels / data / nodes / edges / rows,
     // the edge keys, the sample keys and their sorted copy, sort temp, counters (append, missing, bad edges)
     DevBuf ef_lab, ef_data, ef_nodes, ef_edges, ef_out, ef_ekeys, ef_keys, ef_skeys, ef_tmp, ef_red;
+    // NodeLabelWorkflow (k_overlaps.hip): host-pointer staging of the second label array (the
+    // fragments take rg_lab), the rows (m x 3); everything else is the graph path's
+    DevBuf ov_lab, ov_rows;
     int64_t sf_n = 0;
     uint64_t sf_lo = 1, sf_hi = 0;
     bool sf_has_bits = false;
@@ -2549,7 +2552,8 @@ void ctws_close(ctws_handle* h) {
                     h->tc_red.p, h->tc_in.p, h->tc_mask.p, h->tc_out.p, h->tc_raw.p, h->tc_tmp.p, h->tc_taps.p,
                     h->rg_lab.p, h->rg_tab.p, h->rg_nodes.p, h->rg_pairs.p, h->rg_w.p, h->rg_keys.p, h->rg_skeys.p, h->rg_sw.p,
                     h->rg_sum.p, h->rg_out.p, h->rg_tmp.p, h->rg_red.p, h->ef_lab.p, h->ef_data.p, h->ef_nodes.p,
-                    h->ef_edges.p, h->ef_out.p, h->ef_ekeys.p, h->ef_keys.p, h->ef_skeys.p, h->ef_tmp.p, h->ef_red.p};
+                    h->ef_edges.p, h->ef_out.p, h->ef_ekeys.p, h->ef_keys.p, h->ef_skeys.p, h->ef_tmp.p, h->ef_red.p,
+                    h->ov_lab.p, h->ov_rows.p};
     for (void* p : ptrs)
         if (p) hipFree(p);
     for (auto e : h->events) hipEventDestroy(e);
@@ -3445,6 +3449,120 @@ int ctws_rag_block_device(ctws_handle* h, const uint64_t* labels, int64_t nz, in
                      true);
 }
 
+
+// ---- NodeLabelWorkflow: fragment / label overlaps (k_overlaps.hip) ---------------------------
+extern "C++" {
+namespace {
+int label_overlaps(ctws_handle* h, const uint64_t* nodes_vol, const uint64_t* labels_vol, int64_t n, int with_ignore,
+                   uint64_t ignore_label, uint64_t* rows, int64_t cap, int64_t* n_rows, bool dev) {
+    if (!h || n < 0 || ((!nodes_vol || !labels_vol) && n > 0) || !n_rows || cap < 0 || (!rows && cap > 0))
+        return CTWS_EINVAL;
+    h->err.clear();
+    h->timings.clear();
+    HIPCHK(hipSetDevice(h->device));
+    *n_rows = 0;
+    if (n == 0) return CTWS_OK;
+    if (n >= (1ll << 31)) {
+        h->err = "label overlaps: 2^31 or more voxels in one call (the pair kernel indexes the arrays with 32 bits)";
+        return CTWS_EUNSUPPORTED;
+    }
+    int r;
+    const size_t nb = sizeof(uint64_t) * (size_t)n;
+    const uint64_t *dn = nodes_vol, *dl = labels_vol;
+    if (!dev) {
+        if ((r = grow(h, h->rg_lab, nb)) != CTWS_OK) return r;
+        if ((r = grow(h, h->ov_lab, nb)) != CTWS_OK) return r;
+        HIPCHK(copy_pieces(h->rg_lab.p, nodes_vol, nb, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(copy_pieces(h->ov_lab.p, labels_vol, nb, hipMemcpyHostToDevice, h->stream));
+        dn = (const uint64_t*)h->rg_lab.p;
+        dl = (const uint64_t*)h->ov_lab.p;
+    }
+    // the run heads: a first buffer of a quarter of the voxels (the size depends on n alone, so a
+    // call behaves the same whatever the handle ran before); the emission is repeated with the
+    // counted size when it did not fit -- at most one emit per voxel
+    if ((r = grow(h, h->rg_red, kRagRed * sizeof(uint64_t))) != CTWS_OK) return r;
+    unsigned long long* cnt = (unsigned long long*)h->rg_red.p;
+    OvArgs a;
+    a.nodes = dn;
+    a.labels = dl;
+    a.n = (uint32_t)n;
+    a.with_ignore = with_ignore ? 1 : 0;
+    a.ignore_label = ignore_label;
+    a.count = cnt;
+    const int64_t words = (n + 63) / 64;
+    // four workgroups per CU, as k_rag_pairs: every wave ends with an append of its own
+    const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>((words + 3) / 4, 1024));
+    unsigned long long emitted = 0;
+    unsigned long long ecap = (unsigned long long)std::max<int64_t>(64, n / 4);
+    record(h, 0);
+    int attempt = 0;
+    for (; attempt < 2; ++attempt) {
+        if ((r = grow(h, h->rg_pairs, 2 * sizeof(uint64_t) * (size_t)ecap)) != CTWS_OK) return r;
+        if ((r = grow(h, h->rg_w, sizeof(uint64_t) * (size_t)ecap)) != CTWS_OK) return r;
+        a.pairs = (uint64_t*)h->rg_pairs.p;
+        a.weights = (uint64_t*)h->rg_w.p;
+        a.cap = ecap;
+        HIPCHK(hipMemsetAsync(cnt, 0, sizeof(uint64_t), h->stream));
+        k_ov_pairs<<<g, 256, 0, h->stream>>>(a);
+        LAUNCHCHK();
+        HIPCHK(hipMemcpyAsync(&emitted, cnt, sizeof(emitted), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (emitted <= ecap) break;
+        if (attempt == 1 || emitted > (unsigned long long)n) {
+            h->err = "label overlaps: the emit count changed between two passes over the same arrays";
+            return CTWS_EHIP;
+        }
+        ecap = emitted;
+    }
+    record(h, 1);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    rag_time(h, "ov_pairs", 0, 1);
+    add_timing(h, "ov_pair_passes", (float)(attempt + 1));  // (counts, as the flood's rounds)
+    add_timing(h, "ov_emits", (float)emitted);
+    if (emitted == 0) return CTWS_OK;  // every voxel carries the ignore label
+    if (emitted >= (1ull << 30)) {
+        h->err = "label overlaps: 2^30 or more runs of equal (node, label) pairs in one call";
+        return CTWS_EUNSUPPORTED;
+    }
+    // ids -> ranks in one table for both sides: the key order is the (node, label) order
+    int64_t nt = 0, m = 0;
+    if ((r = rag_table(h, (const uint64_t*)h->rg_pairs.p, 2 * (int64_t)emitted, &nt)) != CTWS_OK) return r;
+    record(h, 7);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    rag_time(h, "ov_table", 1, 7);
+    if ((r = pairs_tail(h, (const uint64_t*)h->rg_pairs.p, (const uint64_t*)h->rg_w.p, (int64_t)emitted,
+                        (const uint64_t*)h->rg_tab.p, nt, &m)) != CTWS_OK)
+        return r;
+    *n_rows = m;
+    if (m > cap) {
+        h->err = "label overlaps: output capacity too small";
+        return CTWS_EINVAL;
+    }
+    const size_t rb = 3 * sizeof(uint64_t) * (size_t)m;
+    uint64_t* drows = rows;
+    if (!dev) {
+        if ((r = grow(h, h->ov_rows, rb)) != CTWS_OK) return r;
+        drows = (uint64_t*)h->ov_rows.p;
+    }
+    const unsigned gm = (unsigned)std::min<int64_t>((m + 255) / 256, 8192);
+    k_ov_rows<<<gm, 256, 0, h->stream>>>((const uint64_t*)h->rg_out.p, (const uint64_t*)h->rg_sum.p, m, drows);
+    LAUNCHCHK();
+    if (!dev) HIPCHK(hipMemcpyAsync(rows, drows, rb, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return CTWS_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int ctws_label_overlaps(ctws_handle* h, const uint64_t* nodes_vol, const uint64_t* labels_vol, int64_t n,
+                        int with_ignore, uint64_t ignore_label, uint64_t* rows, int64_t cap, int64_t* n_rows) {
+    return label_overlaps(h, nodes_vol, labels_vol, n, with_ignore, ignore_label, rows, cap, n_rows, false);
+}
+
+int ctws_label_overlaps_device(ctws_handle* h, const uint64_t* nodes_vol, const uint64_t* labels_vol, int64_t n,
+                               int with_ignore, uint64_t ignore_label, uint64_t* rows, int64_t cap, int64_t* n_rows) {
+    return label_overlaps(h, nodes_vol, labels_vol, n, with_ignore, ignore_label, rows, cap, n_rows, true);
+}
 
 // ---- EdgeFeaturesWorkflow: boundary-map statistics per edge (k_edgefeat.hip) ----------------
 extern "C++" {

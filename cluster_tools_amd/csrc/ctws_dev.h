@@ -235,6 +235,13 @@ __device__ __forceinline__ bool bit_of(const uint64_t* bits, const BlockDesc& B,
     return (bits[B.fbase + (int64_t)row * ((B.X + 63) >> 6) + (x >> 6)] >> (x & 63)) & 1ull;
 }
 
+// lanes following `lane` that continue its run: cont has a bit for every lane whose pair equals
+// its predecessor's (k_rag.hip, k_overlaps.hip: only run heads are emitted, with this weight)
+__device__ __forceinline__ uint32_t rag_run_len(uint64_t cont, uint32_t lane) {
+    if (lane == 63) return 1u;
+    return 1u + (uint32_t)__builtin_ctzll(~(cont >> (lane + 1)));  // (the shift fills with 0: the run ends)
+}
+
 // ---- EDT x pass -> y pass handoff ------------------------------------------------------------
 // One record per (row, 64-voxel word), laid out as the frontier bitmaps' words are (fbase):
 // the word's foreground bits and the x of the nearest foreground voxel of the row before / after

@@ -318,6 +318,20 @@ hipError_t pair_sort(void* tmp, size_t& bytes, const uint64_t* keys_in, uint64_t
                      uint64_t* w_out, int64_t n, int end_bit, hipStream_t stream);
 hipError_t pair_reduce(void* tmp, size_t& bytes, const uint64_t* keys, uint64_t* uniq, const uint64_t* w,
                        uint64_t* sums, uint64_t* n_runs, int64_t n, hipStream_t stream);
+// k_overlaps.hip (NodeLabelWorkflow: the (node, label) pairs of two label arrays, as weighted run heads)
+struct OvArgs {
+    const uint64_t* nodes;      // the fragments, n voxels
+    const uint64_t* labels;     // the second label array, n voxels
+    uint32_t n;                 // n < 2^31
+    int with_ignore;            // voxels with labels[i] == ignore_label are not counted
+    uint64_t ignore_label;
+    uint64_t* pairs;            // out: (node, label) per emit, cap x 2
+    uint64_t* weights;          // out: the emit's run length
+    unsigned long long cap;     // emits at positions >= cap are counted, not written
+    unsigned long long* count;  // the append counter
+};
+__global__ void k_ov_pairs(OvArgs);
+__global__ void k_ov_rows(const uint64_t*, const uint64_t*, int64_t, uint64_t*);
 // k_edgefeat.hip (EdgeFeaturesWorkflow: the boundary-map statistics of a block's edges)
 struct EfArgs {
     const uint64_t* lab;          // the block's labels, (nz, ny, nx): the extended box

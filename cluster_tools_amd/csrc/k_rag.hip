@@ -37,13 +37,6 @@
 
 namespace ctws {
 
-// lanes following `lane` that continue its run: cont has a bit for every lane whose pair equals
-// its predecessor's
-__device__ __forceinline__ uint32_t rag_run_len(uint64_t cont, uint32_t lane) {
-    if (lane == 63) return 1u;
-    return 1u + (uint32_t)__builtin_ctzll(~(cont >> (lane + 1)));  // (the shift fills with 0: the run ends)
-}
-
 constexpr int kRagStage = 512;      // staged emits per wave (a step emits at most 3 * 64)
 constexpr int kRagNodeStage = 128;  // staged node emits per wave (a step emits at most 64)
 

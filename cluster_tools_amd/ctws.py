@@ -70,6 +70,9 @@ def lib():
                 getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int,
                                            C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p,
                                            C.c_int64, C.POINTER(C.c_int64)]
+            for fn in ('ctws_label_overlaps', 'ctws_label_overlaps_device'):
+                getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_uint64,
+                                           C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
             for fn in ('ctws_edge_features_block', 'ctws_edge_features_block_device'):
                 getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_int64] * 6 + [
                     C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]
@@ -98,7 +101,8 @@ EXPORTED_SYMBOLS = ('ctws_abi_version', 'ctws_open', 'ctws_close', 'ctws_last_er
                     'ctws_eval_begin', 'ctws_eval_add', 'ctws_eval_end', 'ctws_threshold_components',
                     'ctws_threshold_components_ex', 'ctws_ufd_find', 'ctws_set_discard_u64', 'ctws_size_filter_blocks',
                     'ctws_size_filter_blocks_device', 'ctws_unique_pairs_u64', 'ctws_rag_block', 'ctws_rag_block_device',
-                    'ctws_edge_features_block', 'ctws_edge_features_block_device')
+                    'ctws_edge_features_block', 'ctws_edge_features_block_device', 'ctws_label_overlaps',
+                    'ctws_label_overlaps_device')
 
 
 def ufd_find(n_labels, pairs):
@@ -725,5 +729,76 @@ class Handle:
                                                           out.data_ptr(), C.byref(miss)),
                     'ctws_edge_features_block_device')
         return out, int(miss.value)
+
+    # ---- NodeLabelWorkflow kernels ---------------------------------------------------------
+    # first capacity of label_overlaps in rows: a call that does not fit computes everything again
+    OVERLAP_CAP = 1 << 18
+
+    @staticmethod
+    def _ignore_args(ignore_label):
+        """(with_ignore, ignore_label as uint64) of the C call; a negative label wraps as .astype does"""
+        if ignore_label is None:
+            return 0, 0
+        return 1, int(ignore_label) & 0xFFFFFFFFFFFFFFFF
+
+    def label_overlaps_raw(self, nodes_vol, labels_vol, ignore_label, cap):
+        """One ctws_label_overlaps call with an output of `cap` rows: (return code, n_rows,
+        rows (cap, 3)).  nodes_vol and labels_vol are uint64 arrays of one size."""
+        nodes_vol = np.ascontiguousarray(nodes_vol, dtype=np.uint64)
+        labels_vol = np.ascontiguousarray(labels_vol, dtype=np.uint64)
+        assert nodes_vol.size == labels_vol.size, (nodes_vol.shape, labels_vol.shape)
+        rows = np.empty((cap, 3), dtype=np.uint64)
+        n = C.c_int64(0)
+        wi, il = self._ignore_args(ignore_label)
+        size = nodes_vol.size
+        ret = lib().ctws_label_overlaps(self._h, nodes_vol.ctypes.data if size else None,
+                                        labels_vol.ctypes.data if size else None, size, wi, il,
+                                        rows.ctypes.data if cap else None, cap, C.byref(n))
+        return ret, int(n.value), rows
+
+    def label_overlaps(self, nodes_vol, labels_vol, ignore_label=None):
+        """The overlaps of the fragments nodes_vol (uint64) with a second label volume of the same
+        shape (include/ctws.h, ctws_label_overlaps): rows (m, 3) uint64 of (node, label, count),
+        sorted by (node, label), count = the voxels with that pair.  labels_vol of any integer dtype
+        is taken as .astype('uint64'), as the reference does.  ignore_label not None: voxels whose
+        label equals it are not counted.  A call that hits the capacity is repeated once with the
+        returned size."""
+        nodes_vol = np.asarray(nodes_vol)
+        labels_vol = np.asarray(labels_vol)
+        if nodes_vol.dtype != np.dtype('uint64'):
+            raise TypeError("label overlaps: the fragments are uint64, not %s" % nodes_vol.dtype)
+        if labels_vol.dtype.kind not in 'iu':
+            raise TypeError("label overlaps: the labels are integers, not %s" % labels_vol.dtype)
+        if nodes_vol.shape != labels_vol.shape:
+            raise ValueError("label overlaps: fragments and labels are of one shape, not %s and %s"
+                             % (nodes_vol.shape, labels_vol.shape))
+        labels_vol = labels_vol.astype('uint64', copy=False)
+        cap = self.OVERLAP_CAP
+        ret, m, rows = self.label_overlaps_raw(nodes_vol, labels_vol, ignore_label, cap)
+        if ret == -1 and m > cap:
+            ret, m, rows = self.label_overlaps_raw(nodes_vol, labels_vol, ignore_label, m)
+        self._check(ret, 'ctws_label_overlaps')
+        return rows[:m]
+
+    def label_overlaps_device(self, nodes_vol, labels_vol, ignore_label=None):
+        """label_overlaps on two uint64 / int64 torch tensors of one size on this GPU; the rows come
+        back as an int64 tensor (uint64 bits) on the same device: only their number crosses PCIe."""
+        import torch
+        for t in (nodes_vol, labels_vol):
+            assert t.is_cuda and t.is_contiguous() and t.element_size() == 8 and not t.is_floating_point()
+        assert nodes_vol.numel() == labels_vol.numel(), (nodes_vol.shape, labels_vol.shape)
+        torch.cuda.current_stream(nodes_vol.device).synchronize()
+        wi, il = self._ignore_args(ignore_label)
+        n = C.c_int64(0)
+        cap = self.OVERLAP_CAP
+        for _ in range(2):
+            rows = torch.empty((cap, 3), dtype=torch.int64, device=nodes_vol.device)
+            ret = lib().ctws_label_overlaps_device(self._h, nodes_vol.data_ptr(), labels_vol.data_ptr(),
+                                                   nodes_vol.numel(), wi, il, rows.data_ptr(), cap, C.byref(n))
+            if not (ret == -1 and n.value > cap):
+                break
+            cap = n.value
+        self._check(ret, 'ctws_label_overlaps_device')
+        return rows[:n.value]
 
     # ---- multi-GPU label-count exchange (RCCL) ------------------------------------------

@@ -124,6 +124,7 @@ class Dataset:
         self._cache = OrderedDict()
         self._cache_used = 0
         self._cache_lock = threading.Lock()
+        self._varlen = set()  # ids of the chunks read in n5's variable-length mode
         if fmt == 'n5':
             with open(os.path.join(path, 'attributes.json')) as f:
                 meta = json.load(f)
@@ -198,10 +199,19 @@ class Dataset:
             raw = f.read()
         beg, end = self._chunk_bb(cid)
         if self.fmt == 'n5':
-            mode, nd = np.frombuffer(raw[:4], dtype='>u2')
-            assert mode == 0, "varlength n5 chunks are not supported"
+            mode, nd = (int(v) for v in np.frombuffer(raw[:4], dtype='>u2'))
+            if mode not in (0, 1):
+                raise ValueError("n5 chunk %s has mode %i (0: fixed size, 1: variable length)" % (p, mode))
             cshape = tuple(np.frombuffer(raw[4:4 + 4 * nd], dtype='>u4')[::-1].astype(int))
-            data = _decompress(raw[4 + 4 * nd:], self.compression,
+            off = 4 + 4 * nd
+            if mode == 1:
+                # variable length: the element count follows the nominal dims, the data is 1-D
+                cshape = (int(np.frombuffer(raw[off:off + 4], dtype='>u4')[0]),)
+                off += 4
+                self._varlen.add(tuple(cid))
+            else:
+                self._varlen.discard(tuple(cid))
+            data = _decompress(raw[off:], self.compression,
                                int(np.prod(cshape)) * self.dtype.itemsize)
             arr = data.view(self.dtype.newbyteorder('>')).reshape(cshape)
             if not arr.flags.writeable:
@@ -212,15 +222,29 @@ class Dataset:
         arr = data.view(self.dtype).reshape(self.chunks)
         return arr[tuple(slice(0, e - b) for b, e in zip(beg, end))]
 
-    def write_chunk(self, cid, arr):
+    def write_chunk(self, cid, arr, varlen=False):
+        """Write one chunk: `arr` has the chunk's valid shape; with varlen=True (n5 only, z5py's
+        `write_chunk(cid, arr, True)`) it is 1-D, of the dataset's dtype and of any length, and the
+        chunk is stored in n5's variable-length mode."""
         beg, end = self._chunk_bb(cid)
         valid = tuple(e - b for b, e in zip(beg, end))
-        assert arr.shape == valid, (arr.shape, valid)
+        if varlen:
+            if self.fmt != 'n5':
+                raise NotImplementedError("variable-length chunks exist only in n5 (chunk mode 1); zarr has no "
+                                          "portable form for them (a zarr chunk always holds the full chunk shape)")
+            arr = np.asarray(arr)
+            if arr.ndim != 1 or arr.dtype != self.dtype:
+                raise ValueError("a variable-length chunk is 1-D and of dtype %s, not %i-D %s"
+                                 % (self.dtype, arr.ndim, arr.dtype))
+        else:
+            assert arr.shape == valid, (arr.shape, valid)
         p = self._chunk_path(cid)
         os.makedirs(os.path.dirname(p), exist_ok=True)
         if self.fmt == 'n5':
-            header = np.array([0, len(valid)], dtype='>u2').tobytes() + \
+            header = np.array([1 if varlen else 0, len(valid)], dtype='>u2').tobytes() + \
                 np.array(valid[::-1], dtype='>u4').tobytes()
+            if varlen:
+                header += np.array([arr.size], dtype='>u4').tobytes()
             payload = _compress(np.ascontiguousarray(arr, dtype=self.dtype.newbyteorder('>')), self.compression)
             data = header + payload
         else:
@@ -231,6 +255,12 @@ class Dataset:
         with open(tmp, 'wb') as f:
             f.write(data)
         os.replace(tmp, p)
+
+    def _refuse_varlen(self, cid):
+        """Region access has no meaning for a variable-length chunk: its data is no box of voxels."""
+        if tuple(cid) in self._varlen:
+            raise ValueError("chunk %s of %s is a variable-length n5 chunk: it holds a 1-D sequence, not the "
+                             "voxels of its region; read it with read_chunk" % (tuple(cid), self.path))
 
     def _chunk_ids(self, bb):
         ranges = [range(s.start // c, (s.stop - 1) // c + 1) if s.stop > s.start else range(0)
@@ -260,6 +290,7 @@ class Dataset:
 
         def load(cid):
             data = self.read_chunk(cid)
+            self._refuse_varlen(cid)
             beg, end = self._chunk_bb(cid)
             for k in users[cid]:
                 bb = bbs[k][0]
@@ -292,6 +323,7 @@ class Dataset:
                 chunk = np.ascontiguousarray(value[tuple(src)], dtype=self.dtype)
             else:
                 old = self._read_chunk(cid)
+                self._refuse_varlen(cid)
                 chunk = np.full(tuple(e - b for b, e in zip(beg, end)), self._fill, dtype=self.dtype) \
                     if old is None else old.copy()
                 chunk[tuple(dst)] = value[tuple(src)]

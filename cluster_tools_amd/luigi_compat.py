@@ -41,7 +41,8 @@ except ImportError:
 
     class IntParameter(Parameter):
         def normalize(self, x):
-            return int(x)
+            # (luigi passes None through: NodeLabelWorkflow hands ignore_label=None to its tasks)
+            return None if x is None else int(x)
 
     class FloatParameter(Parameter):
         def normalize(self, x):

@@ -293,6 +293,31 @@ int ctws_rag_block_device(ctws_handle* h, const uint64_t* labels, int64_t nz, in
                           uint64_t* counts, int64_t cap_edges, int64_t* n_edges);
 
 /*
+ * NodeLabelWorkflow (node_labels/node_label_workflow.py), BlockNodeLabels: the overlaps of the
+ * fragments with a second label volume (block_node_labels.py:130-170,
+ * `ndist.computeAndSerializeLabelOverlaps`, restated: DESIGN.md section 3.6).
+ *
+ * ctws_label_overlaps / _device: nodes_vol and labels_vol are two uint64 arrays of n voxels each;
+ *   only the voxel correspondence matters, so there is no shape.
+ *     rows    m x 3 uint64, C order: (node, label, count) for every pair that occurs at a counted
+ *             voxel, sorted lexicographically by (node, label); count = the voxels with that pair
+ *     with_ignore != 0: voxels whose LABEL equals ignore_label are not counted (`withIgnoreLabel`
+ *             / `ignoreLabel`, block_node_labels.py:153-156).  Voxels of node 0 are counted like
+ *             any other.
+ *   *n_rows is always set; CTWS_EINVAL when cap (in rows) is too small (nothing written: retry
+ *   with that size).  Every uint64 value is a legal id on both sides, 2^64 - 1 included.  The rows
+ *   depend on the inputs alone (repeated calls agree byte for byte).  Fewer than 2^31 voxels, 2^30
+ *   runs of equal pairs in scan order and 2^32 distinct values (node and label ids together) per
+ *   call: the limits of the path behind ctws_unique_pairs_u64, which sorts and sums the runs
+ *   (CTWS_EUNSUPPORTED otherwise).  Host pointers are staged through HBM; _device takes device
+ *   pointers on the handle's GPU for nodes_vol, labels_vol and rows.
+ */
+int ctws_label_overlaps(ctws_handle* h, const uint64_t* nodes_vol, const uint64_t* labels_vol, int64_t n,
+                        int with_ignore, uint64_t ignore_label, uint64_t* rows, int64_t cap, int64_t* n_rows);
+int ctws_label_overlaps_device(ctws_handle* h, const uint64_t* nodes_vol, const uint64_t* labels_vol, int64_t n,
+                               int with_ignore, uint64_t ignore_label, uint64_t* rows, int64_t cap, int64_t* n_rows);
+
+/*
  * EdgeFeaturesWorkflow (features/features_workflow.py:14-66), BlockEdgeFeatures: the boundary-map
  * statistics of the edges of one block (block_edge_features.py:113-132,
  * `ndist.extractBlockFeaturesFromBoundaryMaps_*`, restated: DESIGN.md section 3.5).
