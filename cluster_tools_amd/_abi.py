@@ -101,6 +101,11 @@ def make_cfg(config, block_shape, pass_id=0):
     cfg.invert_inputs = int(bool(config.get('invert_inputs', False)))
     cfg.channel_begin = int(config.get('channel_begin', 0))
     ce = config.get('channel_end', None)
+    if ce is not None and int(ce) < 0:
+        # the reference's slice(channel_begin, -k) drops the last k channels, but in the struct a
+        # negative channel_end is the encoding of None (every channel): refuse, never conflate
+        raise ValueError("channel_end = %r: a negative channel_end cannot be passed to the library (there "
+                         "-1 encodes None); slice the channels on the host, or give the non-negative end" % (ce,))
     cfg.channel_end = -1 if ce is None else int(ce)
     agg = config.get('agglomerate_channels', 'mean')
     assert agg in ('mean', 'max', 'min')

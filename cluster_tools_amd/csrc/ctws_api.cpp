@@ -807,6 +807,16 @@ void add_timing(ctws_handle* h, const char* name, float v) {
     h->timings.push_back({name, v});
 }
 
+// an entry that names something of the last batch (prep_kernel): replaced, not summed
+void set_timing(ctws_handle* h, const char* name, float v) {
+    for (auto& t : h->timings)
+        if (std::strcmp(t.first, name) == 0) {
+            t.second = v;
+            return;
+        }
+    h->timings.push_back({name, v});
+}
+
 // ---- WatershedFromSeeds seeds (k_seeded.hip) ----------------------------------------------
 // The blocks' distinct seed values (hash), sorted per block (segmented radix sort), a label
 // per value = 1 + its rank; blocks without any seed get the strict minima of the hmap
@@ -1112,7 +1122,11 @@ int run_batch(ctws_handle* h, const ctws_cfg* cfg, const Plan& pl, ctws_block* b
     // per word, in w.key: free until the seeds are labelled) instead of g2 per voxel in w.A
     bool edt_bits = false;
     EdtRec* const edt_rec = (EdtRec*)w.key;
+    // the x-pass kernel of this batch, for ctws_last_timings (include/ctws.h): 0 the generic LDS
+    // kernel, KMAX (+ 100 with BITS) k_prep_edt_x_co, 200 + KMAX k_prep_edt_x_reg, -1 the fill
+    int prep_kernel = 0;
     if (pl.sf_fill) {
+        prep_kernel = -1;
         // the height map as it is stored: no min / max, normalize or EDT pass
         k_sf_hmap<<<vg, 256, 0, h->stream>>>(w.desc, w.hm);
         k_fs_active<<<(nb + 255) / 256, 256, 0, h->stream>>>(w.desc, w.stat, nb);
@@ -1149,6 +1163,7 @@ int run_batch(ctws_handle* h, const ctws_cfg* cfg, const Plan& pl, ctws_block* b
         auto launch_co = [&](auto kmax_c, auto bits_c) {
             constexpr int KM = decltype(kmax_c)::value;
             constexpr bool BITS = decltype(bits_c)::value;
+            prep_kernel = KM + (BITS ? 100 : 0);
             auto go = [&](auto kern) { kern<<<gx, 256, 0, h->stream>>>(w.desc, w.stat, pp, fin_out, (uint32_t*)w.A, edt_rec); };
             if (dt == CTWS_U8) go(k_prep_edt_x_co<KM, uint8_t, BITS>);
             else if (dt == CTWS_U16) go(k_prep_edt_x_co<KM, uint16_t, BITS>);
@@ -1161,13 +1176,16 @@ int run_batch(ctws_handle* h, const ctws_cfg* cfg, const Plan& pl, ctws_block* b
             launch_co(std::integral_constant<int, 8>(), std::true_type());
         else if (edt_bits)
             launch_co(std::integral_constant<int, 16>(), std::true_type());
-        else if (typed && all_exact && maxX == 256)
+        else if (typed && all_exact && maxX == 256) {
+            prep_kernel = 200 + 4;
             k_prep_edt_x_reg<4><<<gx, 256, 0, h->stream>>>(w.desc, w.stat, pp, fin_out, (uint32_t*)w.A);
-        else if (typed && all_exact && maxX == 512)
+        } else if (typed && all_exact && maxX == 512) {
+            prep_kernel = 200 + 8;
             k_prep_edt_x_reg<8><<<gx, 256, 0, h->stream>>>(w.desc, w.stat, pp, fin_out, (uint32_t*)w.A);
-        else if (typed && all_exact && maxX == 1024)
+        } else if (typed && all_exact && maxX == 1024) {
+            prep_kernel = 200 + 16;
             k_prep_edt_x_reg<16><<<gx, 256, 0, h->stream>>>(w.desc, w.stat, pp, fin_out, (uint32_t*)w.A);
-        else if (typed && maxX <= 256)
+        } else if (typed && maxX <= 256)
             launch_co(std::integral_constant<int, 4>(), std::false_type());
         else if (typed && maxX <= 512)
             launch_co(std::integral_constant<int, 8>(), std::false_type());
@@ -1183,6 +1201,7 @@ int run_batch(ctws_handle* h, const ctws_cfg* cfg, const Plan& pl, ctws_block* b
         LAUNCHCHK();
     }
     mark("prep_edt_x");
+    set_timing(h, "prep_kernel", (float)prep_kernel);
     bool packed = true;
     uint32_t max_seeds = 0;  // sizes the LDS histogram of the size filter
     std::vector<BlockStat> s2(nb);
@@ -2886,7 +2905,10 @@ int sf_blocks(ctws_handle* h, ctws_block* blocks, int n, int fill, bool dev) {
     h->err = errs;
     if (r != CTWS_OK && errs.find(last) == std::string::npos) h->err += last;
     h->timings.clear();
-    for (auto& t : timings) add_timing(h, t.first, t.second);
+    for (auto& t : timings) {
+        if (std::strcmp(t.first, "prep_kernel") == 0) set_timing(h, t.first, t.second);
+        else add_timing(h, t.first, t.second);
+    }
     return r;
 }
 

@@ -115,7 +115,10 @@ typedef struct ctws_cfg {
     double  pixel_pitch[3];
     int32_t invert_inputs;           /* 'invert_inputs'                                    */
     int32_t channel_begin;           /* 'channel_begin'                                    */
-    int32_t channel_end;             /* 'channel_end', < 0 means None                      */
+    int32_t channel_end;             /* 'channel_end', < 0 means None (every channel): NOT */
+                                     /* python's negative index.  A config's negative end  */
+                                     /* (slice(b, -1) drops the last channel) has to be    */
+                                     /* resolved by the caller; _abi.make_cfg refuses it   */
     int32_t agglomerate_channels;    /* CTWS_AGG_*                                         */
     int32_t non_maximum_suppression; /* must be 0: nifty NMS is not available (:20-23)     */
     int32_t pass_id;                 /* 0 = _ws_block, 1 = _ws_pass2                       */
@@ -232,6 +235,16 @@ int ctws_eval_end(ctws_handle* h, double* scores /* [4] */, int64_t* n_points);
 /*
  * Stage timings of the last ctws_ws_blocks* call, measured with HIP events on the
  * handle's stream (milliseconds).  names[i] is a static string.  Returns the count.
+ * Some entries are counters, not times, summed over the call's batches (flood_rounds,
+ * flood_packed, sf_sparse_blocks, sf_redo_blocks, host_batches, ...).  One names a kernel and is
+ * that of the call's last batch: prep_kernel, the normalize + EDT x pass --
+ *     0            the generic LDS row kernel k_prep_edt_x (4-D input, rows > 1024 voxels,
+ *                  blocks of different dtypes in one batch) with the generic k_input_minmax
+ *     4, 8, 16     k_prep_edt_x_co<KMAX, T, false>
+ *     104, 108, 116  k_prep_edt_x_co<KMAX, T, true> (foreground bits for the y pass)
+ *     204, 208, 216  k_prep_edt_x_reg<KMAX> (float32 rows of exactly 256 / 512 / 1024 voxels)
+ *     -1           the filling size filter (no prep pass: the height map as stored)
+ * The typed k_input_minmax_t<T> ran exactly when the value is positive.
  */
 int ctws_last_timings(const ctws_handle* h, const char** names, float* ms, int max_entries);
 

@@ -196,7 +196,13 @@ def _dtype_cases():
     big = np.int64(2 ** 24 + 1)
     i32 = np.where(rng.random(sh) > .5, big, big - 1).astype(np.int32)      # 2^24 and 2^24+1 are one float32
     u64 = np.where(rng.random(sh) > .5, 2 ** 53 + 2, 2 ** 40).astype(np.uint64)
-    return [('f64_straddle', f64, thr, 'greater', m), ('f64_less', f64, thr, 'less', m),
+    # uint16 over its whole range (both bytes in use), 65535 on a twentieth of the voxels
+    # (a generator of its own: the other rows keep their values)
+    rng16 = np.random.default_rng(16)
+    u16 = rng16.integers(0, 65536, sh).astype(np.uint16)
+    u16[rng16.random(sh) < .05] = 65535
+    return [('u16_greater', u16, 40000.5, 'greater', m), ('u16_equal_max', u16, 65535.0, 'equal', m),
+            ('f64_straddle', f64, thr, 'greater', m), ('f64_less', f64, thr, 'less', m),
             ('i32_equal_2p24', i32, float(big), 'equal', m), ('i32_greater', i32, float(big - 1), 'greater', m),
             ('u64_greater', u64, 2.0 ** 41, 'greater', m),
             ('u8_raw', rng.integers(0, 256, sh).astype(np.uint8), 99.5, 'greater', m),
@@ -218,7 +224,7 @@ def test_block_components_raw_dtypes_match_numpy(gpu_handle, case):
 
 
 @pytest.mark.parametrize('sigma', [1.0, 2.0])
-@pytest.mark.parametrize('kind', ['unmasked', 'masked', 'channel_sum_u8', 'f64_unmasked'])
+@pytest.mark.parametrize('kind', ['unmasked', 'masked', 'channel_sum_u8', 'f64_unmasked', 'u16'])
 def test_block_components_sigma_prefilter_match_oracle(gpu_handle, kind, sigma):
     """sigma_prefilter > 0 (block_components.py:160-162 / :208-211): vigra gaussianSmoothing and
     normalize on the GPU, bit-exact against the oracle's vigra restatement."""
@@ -233,7 +239,9 @@ def test_block_components_sigma_prefilter_match_oracle(gpu_handle, kind, sigma):
         x = (x * 120).astype(np.uint8) + rng.integers(0, 3, sh).astype(np.uint8)
     elif kind == 'f64_unmasked':
         x = x.astype(np.float64) * 3 - 1
-    prenorm = kind in ('unmasked', 'f64_unmasked') or mask is not None
+    elif kind == 'u16':
+        x = (1000 + np.round(64535 * x)).astype(np.uint16)
+    prenorm = kind in ('unmasked', 'f64_unmasked', 'u16') or mask is not None
     lab, n = gpu_handle.threshold_components(x, .5, 'greater', mask=mask, normalize=prenorm, sigma=sigma)
     ref, rn = T.block_components(x, .5, 'greater', mask, normalize_input=prenorm and mask is None, sigma=sigma)
     assert rn > 0 and n == rn
