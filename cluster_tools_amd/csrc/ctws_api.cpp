@@ -136,6 +136,9 @@ struct ctws_handle {
     // NodeLabelWorkflow (k_overlaps.hip): host-pointer staging of the second label array (the
     // fragments take rg_lab), the rows (m x 3); everything else is the graph path's
     DevBuf ov_lab, ov_rows;
+    // MorphologyWorkflow (k_morph.hip): the rows (m x 11) of the host-pointer path; the labels,
+    // records and sort buffers are the graph path's
+    DevBuf mo_rows, mo_acc;  // + the per-id integer table of the segments split over several waves
     int64_t sf_n = 0;
     uint64_t sf_lo = 1, sf_hi = 0;
     bool sf_has_bits = false;
@@ -2572,7 +2575,7 @@ void ctws_close(ctws_handle* h) {
                     h->rg_lab.p, h->rg_tab.p, h->rg_nodes.p, h->rg_pairs.p, h->rg_w.p, h->rg_keys.p, h->rg_skeys.p, h->rg_sw.p,
                     h->rg_sum.p, h->rg_out.p, h->rg_tmp.p, h->rg_red.p, h->ef_lab.p, h->ef_data.p, h->ef_nodes.p,
                     h->ef_edges.p, h->ef_out.p, h->ef_ekeys.p, h->ef_keys.p, h->ef_skeys.p, h->ef_tmp.p, h->ef_red.p,
-                    h->ov_lab.p, h->ov_rows.p};
+                    h->ov_lab.p, h->ov_rows.p, h->mo_rows.p, h->mo_acc.p};
     for (void* p : ptrs)
         if (p) hipFree(p);
     for (auto e : h->events) hipEventDestroy(e);
@@ -3584,6 +3587,174 @@ int ctws_label_overlaps(ctws_handle* h, const uint64_t* nodes_vol, const uint64_
 int ctws_label_overlaps_device(ctws_handle* h, const uint64_t* nodes_vol, const uint64_t* labels_vol, int64_t n,
                                int with_ignore, uint64_t ignore_label, uint64_t* rows, int64_t cap, int64_t* n_rows) {
     return label_overlaps(h, nodes_vol, labels_vol, n, with_ignore, ignore_label, rows, cap, n_rows, true);
+}
+
+// ---- MorphologyWorkflow: size, centre and bounding box per id (k_morph.hip) ------------------
+extern "C++" {
+namespace {
+int block_morphology(ctws_handle* h, const uint64_t* labels, int64_t nz, int64_t ny, int64_t nx, const int64_t* begin,
+                     double* rows, int64_t cap, int64_t* n_rows, bool dev) {
+    if (!h || !labels || nz <= 0 || ny <= 0 || nx <= 0 || !begin || !n_rows || cap < 0 || (!rows && cap > 0))
+        return CTWS_EINVAL;
+    h->err.clear();
+    h->timings.clear();
+    *n_rows = 0;
+    if (begin[0] < 0 || begin[1] < 0 || begin[2] < 0) {
+        h->err = "block morphology: a negative begin";
+        return CTWS_EINVAL;
+    }
+    HIPCHK(hipSetDevice(h->device));
+    // the record packs z, y, x0 into 19 bits each; begin + extent <= 2^21 and fewer than 2^31
+    // voxels keep every coordinate sum below 2^52, exact in a double
+    constexpr int64_t kExt = 1ll << 19, kCoord = 1ll << 21, kMax = 1ll << 31;
+    if (nz >= kExt || ny >= kExt || nx >= kExt) {
+        h->err = "block morphology: an extent of 2^19 or more (the run record holds 19 bits per coordinate)";
+        return CTWS_EUNSUPPORTED;
+    }
+    if (nz * ny >= kMax || nz * ny * nx >= kMax) {
+        h->err = "block morphology: 2^31 or more voxels in one block (the run kernel indexes a block with 32 bits)";
+        return CTWS_EUNSUPPORTED;
+    }
+    const int64_t ext[3] = {nz, ny, nx};
+    for (int d = 0; d < 3; ++d)
+        if (begin[d] > kCoord || begin[d] + ext[d] > kCoord) {
+            h->err = "block morphology: begin + extent above 2^21 (the coordinate sums would not be exact doubles)";
+            return CTWS_EUNSUPPORTED;
+        }
+    const int64_t N = nz * ny * nx;
+    int r;
+    const uint64_t* dl = labels;
+    if (!dev) {
+        if ((r = grow(h, h->rg_lab, sizeof(uint64_t) * (size_t)N)) != CTWS_OK) return r;
+        HIPCHK(copy_pieces(h->rg_lab.p, labels, sizeof(uint64_t) * (size_t)N, hipMemcpyHostToDevice, h->stream));
+        dl = (const uint64_t*)h->rg_lab.p;
+    }
+    // the run heads: a first buffer of a quarter of the voxels (the size depends on the block
+    // alone, so a call behaves the same whatever the handle ran before); the emission is repeated
+    // with the counted size when it did not fit -- at most one emit per voxel
+    if ((r = grow(h, h->rg_red, kRagRed * sizeof(uint64_t))) != CTWS_OK) return r;
+    // [0] the append counter on a 128-B line of its own, [16] the largest id, [19] runs
+    unsigned long long* cnt = (unsigned long long*)h->rg_red.p;
+    MorphArgs a;
+    a.lab = dl;
+    a.nz = (uint32_t)nz;
+    a.ny = (uint32_t)ny;
+    a.nx = (uint32_t)nx;
+    a.count = cnt;
+    a.vmax = cnt + 16;
+    const int64_t lines = nz * ny;
+    // four workgroups per CU, as k_rag_pairs: every wave ends with an append of its own
+    const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>((lines + 3) / 4, 1024));
+    unsigned long long emitted = 0;
+    unsigned long long got[17] = {0};
+    unsigned long long ecap = (unsigned long long)std::max<int64_t>(64, N / 4);
+    record(h, 0);
+    int attempt = 0;
+    for (; attempt < 2; ++attempt) {
+        if ((r = grow(h, h->rg_pairs, sizeof(uint64_t) * (size_t)ecap)) != CTWS_OK) return r;
+        if ((r = grow(h, h->rg_w, sizeof(uint64_t) * (size_t)ecap)) != CTWS_OK) return r;
+        a.ids = (uint64_t*)h->rg_pairs.p;
+        a.recs = (uint64_t*)h->rg_w.p;
+        a.cap = ecap;
+        HIPCHK(hipMemsetAsync(cnt, 0, 17 * sizeof(uint64_t), h->stream));
+        k_morph_runs<<<g, 256, 0, h->stream>>>(a);
+        LAUNCHCHK();
+        HIPCHK(hipMemcpyAsync(got, cnt, sizeof(got), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        emitted = got[0];
+        if (emitted <= ecap) break;
+        if (attempt == 1 || emitted > (unsigned long long)N) {
+            h->err = "block morphology: the emit count changed between two passes over the same labels";
+            return CTWS_EHIP;
+        }
+        ecap = emitted;
+    }
+    if (emitted == 0 || emitted > (unsigned long long)N) {
+        h->err = "block morphology: the run kernel counted " + std::to_string(emitted) + " runs";
+        return CTWS_EHIP;
+    }
+    const int64_t n = (int64_t)emitted;  // (< 2^31)
+    record(h, 1);
+    // the largest id (taken by the run pass): the sort's bits, and the 2^53 limit of the id column
+    const unsigned long long vmax = got[16];
+    if (vmax >= (1ull << 53)) {
+        h->err = "block morphology: an id of 2^53 or more (" + std::to_string(vmax) +
+                 ") has no exact place in the float64 table";
+        return CTWS_EUNSUPPORTED;
+    }
+    int bits = 1;
+    while (bits < 53 && (1ull << bits) <= vmax) ++bits;
+    const size_t nb = sizeof(uint64_t) * (size_t)n;
+    size_t tb_sort = 0, tb_rle = 0;
+    HIPCHK(pair_sort(nullptr, tb_sort, nullptr, nullptr, nullptr, nullptr, n, bits, h->stream));
+    HIPCHK(u64_runs(nullptr, tb_rle, nullptr, nullptr, nullptr, nullptr, n, h->stream));
+    if ((r = grow(h, h->rg_skeys, nb)) != CTWS_OK) return r;
+    if ((r = grow(h, h->rg_sw, nb)) != CTWS_OK) return r;
+    if ((r = grow(h, h->rg_keys, nb)) != CTWS_OK) return r;
+    if ((r = grow(h, h->rg_sum, nb)) != CTWS_OK) return r;
+    if ((r = grow(h, h->rg_tmp, std::max(tb_sort, tb_rle))) != CTWS_OK) return r;
+    uint64_t* sids = (uint64_t*)h->rg_skeys.p;
+    uint64_t* srecs = (uint64_t*)h->rg_sw.p;
+    uint64_t* uniq = (uint64_t*)h->rg_keys.p;
+    uint64_t* counts = (uint64_t*)h->rg_sum.p;
+    HIPCHK(pair_sort(h->rg_tmp.p, tb_sort, a.ids, sids, a.recs, srecs, n, bits, h->stream));
+    HIPCHK(u64_runs(h->rg_tmp.p, tb_rle, sids, uniq, counts, (uint64_t*)(cnt + 19), n, h->stream));
+    record(h, 2);
+    unsigned long long runs = 0;
+    HIPCHK(hipMemcpyAsync(&runs, cnt + 19, sizeof(runs), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    rag_time(h, "morph_runs", 0, 1);
+    rag_time(h, "morph_sort", 1, 2);
+    add_timing(h, "morph_run_passes", (float)(attempt + 1));  // (counts, as the flood's rounds)
+    add_timing(h, "morph_emits", (float)emitted);
+    if (runs == 0 || runs > emitted) {
+        h->err = "block morphology: " + std::to_string(runs) + " ids from " + std::to_string(emitted) + " runs";
+        return CTWS_EHIP;
+    }
+    const int64_t m = (int64_t)runs;
+    *n_rows = m;
+    if (m > cap) {
+        h->err = "block morphology: output capacity too small";
+        return CTWS_EINVAL;
+    }
+    const size_t rb = 11 * sizeof(double) * (size_t)m;
+    double* drows = rows;
+    if (!dev) {
+        if ((r = grow(h, h->mo_rows, rb)) != CTWS_OK) return r;
+        drows = (double*)h->mo_rows.p;
+    }
+    // the per-id table of the split segments: ten integers per id, zero = neutral
+    const size_t ab = 10 * sizeof(uint64_t) * (size_t)m;
+    if ((r = grow(h, h->mo_acc, ab)) != CTWS_OK) return r;
+    unsigned long long* acc = (unsigned long long*)h->mo_acc.p;
+    HIPCHK(hipMemsetAsync(acc, 0, ab, h->stream));
+    const MorphBegin b = {(uint64_t)begin[0], (uint64_t)begin[1], (uint64_t)begin[2]};
+    const int64_t waves = m + n / kMorphChunk;  // a wave per id and per whole chunk of records
+    const unsigned gm = (unsigned)std::max<int64_t>(1, std::min<int64_t>((waves + 3) / 4, 2048));
+    k_morph_rows<<<gm, 256, 0, h->stream>>>(sids, srecs, (uint32_t)n, uniq, counts, (uint32_t)m, b, acc, drows);
+    LAUNCHCHK();
+    if (n >= (int64_t)kMorphChunk) {  // (a shorter record list holds no whole chunk: no split segment)
+        const unsigned gl = (unsigned)std::min<int64_t>((m + 255) / 256, 1024);
+        k_morph_long_rows<<<gl, 256, 0, h->stream>>>(uniq, (uint32_t)m, b, acc, drows);
+        LAUNCHCHK();
+    }
+    record(h, 3);
+    if (!dev) HIPCHK(hipMemcpyAsync(rows, drows, rb, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    rag_time(h, "morph_rows", 2, 3);
+    return CTWS_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int ctws_block_morphology(ctws_handle* h, const uint64_t* labels, int64_t nz, int64_t ny, int64_t nx,
+                          const int64_t begin[3], double* rows, int64_t cap, int64_t* n_rows) {
+    return block_morphology(h, labels, nz, ny, nx, begin, rows, cap, n_rows, false);
+}
+
+int ctws_block_morphology_device(ctws_handle* h, const uint64_t* labels, int64_t nz, int64_t ny, int64_t nx,
+                                 const int64_t begin[3], double* rows, int64_t cap, int64_t* n_rows) {
+    return block_morphology(h, labels, nz, ny, nx, begin, rows, cap, n_rows, true);
 }
 
 // ---- EdgeFeaturesWorkflow: boundary-map statistics per edge (k_edgefeat.hip) ----------------

@@ -332,6 +332,26 @@ struct OvArgs {
 };
 __global__ void k_ov_pairs(OvArgs);
 __global__ void k_ov_rows(const uint64_t*, const uint64_t*, int64_t, uint64_t*);
+// k_morph.hip (MorphologyWorkflow: the runs of equal ids along x, then one table row per id)
+struct MorphArgs {
+    const uint64_t* lab;        // the block's labels, (nz, ny, nx)
+    uint32_t nz, ny, nx;        // every extent < 2^19, nz * ny * nx < 2^31
+    uint64_t* ids;              // out: the run's id per emit
+    uint64_t* recs;             // out: z << 44 | y << 25 | x0 << 6 | (len - 1) per emit
+    unsigned long long cap;     // emits at positions >= cap are counted, not written
+    unsigned long long* count;  // the append counter
+    unsigned long long* vmax;   // the largest id of the block (atomicMax; zeroed)
+};
+struct MorphBegin {
+    uint64_t z, y, x;  // the block's begin: begin + extent <= 2^21 per axis
+};
+__global__ void k_morph_runs(MorphArgs);
+// sorted records per chunk of k_morph_rows: an id's segment that holds whole aligned chunks is split
+// over one wave per chunk (measured: DESIGN.md section 3.7)
+constexpr int kMorphChunk = 2048;
+__global__ void k_morph_rows(const uint64_t*, const uint64_t*, uint32_t, const uint64_t*, const uint64_t*, uint32_t,
+                             MorphBegin, unsigned long long*, double*);
+__global__ void k_morph_long_rows(const uint64_t*, uint32_t, MorphBegin, const unsigned long long*, double*);
 // k_edgefeat.hip (EdgeFeaturesWorkflow: the boundary-map statistics of a block's edges)
 struct EfArgs {
     const uint64_t* lab;          // the block's labels, (nz, ny, nx): the extended box

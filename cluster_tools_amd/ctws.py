@@ -73,6 +73,9 @@ def lib():
             for fn in ('ctws_label_overlaps', 'ctws_label_overlaps_device'):
                 getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_uint64,
                                            C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+            for fn in ('ctws_block_morphology', 'ctws_block_morphology_device'):
+                getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                           C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
             for fn in ('ctws_edge_features_block', 'ctws_edge_features_block_device'):
                 getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_int64] * 6 + [
                     C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]
@@ -102,7 +105,7 @@ EXPORTED_SYMBOLS = ('ctws_abi_version', 'ctws_open', 'ctws_close', 'ctws_last_er
                     'ctws_threshold_components_ex', 'ctws_ufd_find', 'ctws_set_discard_u64', 'ctws_size_filter_blocks',
                     'ctws_size_filter_blocks_device', 'ctws_unique_pairs_u64', 'ctws_rag_block', 'ctws_rag_block_device',
                     'ctws_edge_features_block', 'ctws_edge_features_block_device', 'ctws_label_overlaps',
-                    'ctws_label_overlaps_device')
+                    'ctws_label_overlaps_device', 'ctws_block_morphology', 'ctws_block_morphology_device')
 
 
 def ufd_find(n_labels, pairs):
@@ -799,6 +802,67 @@ class Handle:
                 break
             cap = n.value
         self._check(ret, 'ctws_label_overlaps_device')
+        return rows[:n.value]
+
+    # ---- MorphologyWorkflow kernels --------------------------------------------------------
+    # first capacity of block_morphology in rows: a call that does not fit computes everything again
+    MORPHOLOGY_CAP = 1 << 16
+
+    @staticmethod
+    def _begin_arg(begin):
+        begin = [int(b) for b in begin]
+        if len(begin) != 3:
+            raise ValueError("block morphology: begin has three entries, not %s" % (begin,))
+        return (C.c_int64 * 3)(*begin)
+
+    def block_morphology_raw(self, labels, begin, cap):
+        """One ctws_block_morphology call with an output of `cap` rows: (return code, n_rows,
+        rows (cap, 11)).  labels is a 3-D uint64 array; the rows start out as NaN, so a call that
+        writes nothing leaves them so."""
+        labels = np.ascontiguousarray(labels, dtype=np.uint64)
+        assert labels.ndim == 3 and labels.size, labels.shape
+        rows = np.full((cap, 11), np.nan, dtype=np.float64)
+        n = C.c_int64(0)
+        ret = lib().ctws_block_morphology(self._h, labels.ctypes.data, *labels.shape, self._begin_arg(begin),
+                                          rows.ctypes.data if cap else None, cap, C.byref(n))
+        return ret, int(n.value), rows
+
+    def block_morphology(self, labels, begin=(0, 0, 0)):
+        """The morphology table of one block of uint64 labels at offset `begin` of its volume
+        (include/ctws.h, ctws_block_morphology): rows (m, 11) float64 of [id, size, com_z, com_y,
+        com_x, min_z, min_y, min_x, max_z, max_y, max_x], a row per id of the block (0 included),
+        sorted by id, in global coordinates, minima and maxima inclusive.  A call that hits the
+        capacity is repeated once with the returned size."""
+        labels = np.asarray(labels)
+        if labels.dtype != np.dtype('uint64'):
+            raise TypeError("block morphology: the labels are uint64, not %s" % labels.dtype)
+        if labels.ndim != 3 or not labels.size:
+            raise ValueError("block morphology: the labels are a non-empty 3-D block, not %s" % (labels.shape,))
+        cap = self.MORPHOLOGY_CAP
+        ret, m, rows = self.block_morphology_raw(labels, begin, cap)
+        if ret == -1 and m > cap:
+            ret, m, rows = self.block_morphology_raw(labels, begin, m)
+        self._check(ret, 'ctws_block_morphology')
+        return rows[:m]
+
+    def block_morphology_device(self, labels, begin=(0, 0, 0)):
+        """block_morphology on a uint64 / int64 torch tensor on this GPU; the rows come back as a
+        float64 tensor on the same device: only their number crosses PCIe."""
+        import torch
+        assert labels.is_cuda and labels.is_contiguous() and labels.element_size() == 8 and labels.dim() == 3
+        assert labels.numel() > 0 and not labels.is_floating_point()
+        torch.cuda.current_stream(labels.device).synchronize()
+        b = self._begin_arg(begin)
+        n = C.c_int64(0)
+        cap = self.MORPHOLOGY_CAP
+        for _ in range(2):
+            rows = torch.empty((cap, 11), dtype=torch.float64, device=labels.device)
+            ret = lib().ctws_block_morphology_device(self._h, labels.data_ptr(), *labels.shape, b, rows.data_ptr(),
+                                                     cap, C.byref(n))
+            if not (ret == -1 and n.value > cap):
+                break
+            cap = n.value
+        self._check(ret, 'ctws_block_morphology_device')
         return rows[:n.value]
 
     # ---- multi-GPU label-count exchange (RCCL) ------------------------------------------

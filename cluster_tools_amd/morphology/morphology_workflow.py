@@ -1,0 +1,46 @@
+"""MorphologyWorkflow: BlockMorphology -> MergeMorphology
+(cluster_tools/morphology/morphology_workflow.py:11-56; parameters and config keys unchanged): the
+(maxId + 1, 11) float64 table [id, size, com_z, com_y, com_x, min_z, min_y, min_x, max_z, max_y,
+max_x] of a label volume.  The block tables go to `morphology_<prefix>` in the output file.
+RegionCentersWorkflow (:59-94) is not built."""
+from cluster_tools_amd import luigi_compat as luigi
+from cluster_tools_amd.cluster_tasks import WorkflowBase
+from cluster_tools_amd.utils import volume_utils as vu
+from cluster_tools_amd.morphology import block_morphology as block_tasks
+from cluster_tools_amd.morphology import merge_morphology as merge_tasks
+
+
+class MorphologyWorkflow(WorkflowBase):
+    input_path = luigi.Parameter()
+    input_key = luigi.Parameter()
+    output_path = luigi.Parameter()
+    output_key = luigi.Parameter()
+    max_jobs_merge = luigi.Parameter(default=None)
+    prefix = luigi.Parameter(default='')
+
+    def requires(self):
+        common = dict(tmp_folder=self.tmp_folder, config_dir=self.config_dir)
+        tmp_key = 'morphology_%s' % self.prefix
+        block_task = getattr(block_tasks, self._get_task_name('BlockMorphology'))
+        dep = block_task(max_jobs=self.max_jobs, dependency=self.dependency, input_path=self.input_path,
+                         input_key=self.input_key, output_path=self.output_path, output_key=tmp_key,
+                         prefix=self.prefix, **common)
+        with vu.file_reader(self.input_path, 'r') as f:
+            attrs = f[self.input_key].attrs
+            try:
+                number_of_labels = int(attrs['maxId']) + 1
+            except KeyError:
+                raise KeyError("Dataset %s:%s does not have attribute maxId" % (self.input_path, self.input_key))
+        max_jobs_merge = self.max_jobs if self.max_jobs_merge is None else int(self.max_jobs_merge)
+        merge_task = getattr(merge_tasks, self._get_task_name('MergeMorphology'))
+        dep = merge_task(max_jobs=max_jobs_merge, dependency=dep, input_path=self.output_path, input_key=tmp_key,
+                         output_path=self.output_path, output_key=self.output_key,
+                         number_of_labels=number_of_labels, prefix=self.prefix, **common)
+        return dep
+
+    @staticmethod
+    def get_config():
+        configs = WorkflowBase.get_config()
+        configs.update({'block_morphology': block_tasks.BlockMorphologyLocal.default_task_config(),
+                        'merge_morphology': merge_tasks.MergeMorphologyLocal.default_task_config()})
+        return configs

@@ -331,6 +331,33 @@ int ctws_label_overlaps_device(ctws_handle* h, const uint64_t* nodes_vol, const 
                                int with_ignore, uint64_t ignore_label, uint64_t* rows, int64_t cap, int64_t* n_rows);
 
 /*
+ * MorphologyWorkflow (morphology/morphology_workflow.py:11-56), BlockMorphology: size, centre of
+ * mass and bounding box of every id of a block (block_morphology.py:111-136,
+ * `ndist.computeAndSerializeMorphology`, restated: DESIGN.md section 3.7).
+ *
+ * ctws_block_morphology / _device: labels is one block of uint64 ids, shape (nz, ny, nx), C order;
+ *   begin (three values, always a host pointer) is the block's offset in the volume.
+ *     rows    m x 11 float64, C order, a row per id that occurs in the block -- 0 included, there is
+ *             no ignore label -- sorted by id:
+ *             [id, n, com_z, com_y, com_x, min_z, min_y, min_x, max_z, max_y, max_x] over the id's
+ *             voxels at the global coordinates g = begin + local: n = their number, com_a =
+ *             float64(sum of g_a) / float64(n) with the sum taken in integers (one IEEE division),
+ *             min_a and max_a both inclusive.  A block of zeros gives the one row of id 0 (the rule
+ *             that skips such a block is the task's).
+ *   *n_rows is always set; CTWS_EINVAL when cap (in rows) is too small (nothing written: retry
+ *   with that size) or a begin is negative.  Ids below 2^53 (the id column is exact), every extent
+ *   below 2^19, fewer than 2^31 voxels and begin + extent <= 2^21 per axis (every coordinate sum
+ *   stays below 2^52 and converts exactly): CTWS_EUNSUPPORTED otherwise, never a wrong row.  The
+ *   accumulation is integer throughout, so the rows depend on the inputs alone (repeated calls
+ *   agree byte for byte).  Host pointers are staged through HBM; _device takes device pointers on
+ *   the handle's GPU for labels and rows.
+ */
+int ctws_block_morphology(ctws_handle* h, const uint64_t* labels, int64_t nz, int64_t ny, int64_t nx,
+                          const int64_t begin[3], double* rows, int64_t cap, int64_t* n_rows);
+int ctws_block_morphology_device(ctws_handle* h, const uint64_t* labels, int64_t nz, int64_t ny, int64_t nx,
+                                 const int64_t begin[3], double* rows, int64_t cap, int64_t* n_rows);
+
+/*
  * EdgeFeaturesWorkflow (features/features_workflow.py:14-66), BlockEdgeFeatures: the boundary-map
  * statistics of the edges of one block (block_edge_features.py:113-132,
  * `ndist.extractBlockFeaturesFromBoundaryMaps_*`, restated: DESIGN.md section 3.5).
