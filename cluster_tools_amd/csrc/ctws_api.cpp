@@ -139,6 +139,10 @@ struct ctws_handle {
     // MorphologyWorkflow (k_morph.hip): the rows (m x 11) of the host-pointer path; the labels,
     // records and sort buffers are the graph path's
     DevBuf mo_rows, mo_acc;  // + the per-id integer table of the segments split over several waves
+    // RegionFeaturesWorkflow (k_regfeat.hip): host-pointer staging of the input map and the rows
+    // (m x 3), the rows' run counts and their scan, the records' sums, the chunk table (n, sum);
+    // the labels, keys and sort buffers are the graph path's
+    DevBuf rf_data, rf_rows, rf_cnt, rf_off, rf_sums, rf_ctab;
     int64_t sf_n = 0;
     uint64_t sf_lo = 1, sf_hi = 0;
     bool sf_has_bits = false;
@@ -2575,7 +2579,8 @@ void ctws_close(ctws_handle* h) {
                     h->rg_lab.p, h->rg_tab.p, h->rg_nodes.p, h->rg_pairs.p, h->rg_w.p, h->rg_keys.p, h->rg_skeys.p, h->rg_sw.p,
                     h->rg_sum.p, h->rg_out.p, h->rg_tmp.p, h->rg_red.p, h->ef_lab.p, h->ef_data.p, h->ef_nodes.p,
                     h->ef_edges.p, h->ef_out.p, h->ef_ekeys.p, h->ef_keys.p, h->ef_skeys.p, h->ef_tmp.p, h->ef_red.p,
-                    h->ov_lab.p, h->ov_rows.p, h->mo_rows.p, h->mo_acc.p};
+                    h->ov_lab.p, h->ov_rows.p, h->mo_rows.p, h->mo_acc.p, h->rf_data.p, h->rf_rows.p,
+                    h->rf_cnt.p, h->rf_off.p, h->rf_sums.p, h->rf_ctab.p};
     for (void* p : ptrs)
         if (p) hipFree(p);
     for (auto e : h->events) hipEventDestroy(e);
@@ -3755,6 +3760,181 @@ int ctws_block_morphology(ctws_handle* h, const uint64_t* labels, int64_t nz, in
 int ctws_block_morphology_device(ctws_handle* h, const uint64_t* labels, int64_t nz, int64_t ny, int64_t nx,
                                  const int64_t begin[3], double* rows, int64_t cap, int64_t* n_rows) {
     return block_morphology(h, labels, nz, ny, nx, begin, rows, cap, n_rows, true);
+}
+
+// ---- RegionFeaturesWorkflow: count and mean input value per id (k_regfeat.hip) --------------
+extern "C++" {
+namespace {
+int region_features_block(ctws_handle* h, const uint64_t* labels, const void* data, int data_dtype, int64_t nz,
+                          int64_t ny, int64_t nx, int with_ignore, uint64_t ignore_label, double* rows, int64_t cap,
+                          int64_t* n_rows, bool dev) {
+    if (!h || !labels || !data || nz <= 0 || ny <= 0 || nx <= 0 || !n_rows || cap < 0 || (!rows && cap > 0))
+        return CTWS_EINVAL;
+    h->err.clear();
+    h->timings.clear();
+    *n_rows = 0;
+    if (data_dtype != CTWS_U8 && data_dtype != CTWS_U16 && data_dtype != CTWS_F32 && data_dtype != CTWS_F64) {
+        h->err = "region features: the input map is uint8, uint16, float32 or float64";
+        return CTWS_EINVAL;
+    }
+    HIPCHK(hipSetDevice(h->device));
+    constexpr int64_t kMax = 1ll << 31;
+    if (nz >= kMax || ny >= kMax || nx >= kMax || nz * ny >= kMax || nz * ny * nx >= kMax) {
+        h->err = "region features: 2^31 or more voxels in one block (the kernels index a block with 32 bits)";
+        return CTWS_EUNSUPPORTED;
+    }
+    const int64_t N = nz * ny * nx, lines = nz * ny;
+    if (lines + 1 >= kMax) {  // (the scan takes the rows' counts and one 0 behind them with a 32-bit size)
+        h->err = "region features: 2^31 - 1 rows in one block (the scan of the rows' run counts is 32-bit)";
+        return CTWS_EUNSUPPORTED;
+    }
+    const size_t es = data_dtype == CTWS_U8 ? 1 : data_dtype == CTWS_U16 ? 2 : data_dtype == CTWS_F32 ? 4 : 8;
+    int r;
+    const uint64_t* dl = labels;
+    const void* dd = data;
+    if (!dev) {
+        if ((r = grow(h, h->rg_lab, sizeof(uint64_t) * (size_t)N)) != CTWS_OK) return r;
+        if ((r = grow(h, h->rf_data, es * (size_t)N)) != CTWS_OK) return r;
+        HIPCHK(copy_pieces(h->rg_lab.p, labels, sizeof(uint64_t) * (size_t)N, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(copy_pieces(h->rf_data.p, data, es * (size_t)N, hipMemcpyHostToDevice, h->stream));
+        dl = (const uint64_t*)h->rg_lab.p;
+        dd = h->rf_data.p;
+    }
+    if ((r = grow(h, h->rg_red, kRagRed * sizeof(uint64_t))) != CTWS_OK) return r;
+    unsigned long long* red = (unsigned long long*)h->rg_red.p;  // [16] the largest id, [19] the ids' number
+    // the rows' run counts with one 0 behind them: the scan's last entry is the total
+    const size_t cb = sizeof(uint32_t) * (size_t)(lines + 1);
+    size_t tb_scan = 0;
+    HIPCHK(u32_exclusive_sum(nullptr, tb_scan, nullptr, nullptr, lines + 1, h->stream));
+    if ((r = grow(h, h->rf_cnt, cb)) != CTWS_OK) return r;
+    if ((r = grow(h, h->rf_off, cb)) != CTWS_OK) return r;
+    if ((r = grow(h, h->rg_tmp, tb_scan)) != CTWS_OK) return r;
+    uint32_t* rcnt = (uint32_t*)h->rf_cnt.p;
+    uint32_t* roff = (uint32_t*)h->rf_off.p;
+    // four workgroups per CU, a wave per row
+    const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>((lines + 3) / 4, 1024));
+    record(h, 0);
+    HIPCHK(hipMemsetAsync(rcnt + lines, 0, sizeof(uint32_t), h->stream));
+    HIPCHK(hipMemsetAsync(red, 0, kRagRed * sizeof(uint64_t), h->stream));
+    k_regfeat_count<<<g, 256, 0, h->stream>>>(dl, (uint32_t)lines, (uint32_t)nx, rcnt);
+    LAUNCHCHK();
+    HIPCHK(u32_exclusive_sum(h->rg_tmp.p, tb_scan, rcnt, roff, lines + 1, h->stream));
+    record(h, 1);
+    uint32_t total = 0;
+    HIPCHK(hipMemcpyAsync(&total, roff + lines, sizeof(total), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (total == 0 || (int64_t)total > N) {
+        h->err = "region features: the count kernel found " + std::to_string(total) + " runs";
+        return CTWS_EHIP;
+    }
+    const int64_t n = (int64_t)total;  // (< 2^31): the record arrays hold exactly the runs
+    const size_t nb = sizeof(uint64_t) * (size_t)n;
+    if ((r = grow(h, h->rg_pairs, nb)) != CTWS_OK) return r;
+    if ((r = grow(h, h->rg_w, nb)) != CTWS_OK) return r;
+    if ((r = grow(h, h->rf_sums, sizeof(double) * (size_t)n)) != CTWS_OK) return r;
+    RegfeatArgs a;
+    a.lab = dl;
+    a.data = dd;
+    a.rows = (uint32_t)lines;
+    a.nx = (uint32_t)nx;
+    a.with_ignore = with_ignore ? 1 : 0;
+    a.ignore = ignore_label;
+    a.row_first = roff;
+    a.n = total;
+    a.ids = (uint64_t*)h->rg_pairs.p;
+    a.vals = (uint64_t*)h->rg_w.p;
+    a.sums = (double*)h->rf_sums.p;
+    a.vmax = red + 16;
+    if (data_dtype == CTWS_U8) k_regfeat_runs<uint8_t><<<g, 256, 0, h->stream>>>(a);
+    else if (data_dtype == CTWS_U16) k_regfeat_runs<uint16_t><<<g, 256, 0, h->stream>>>(a);
+    else if (data_dtype == CTWS_F32) k_regfeat_runs<float><<<g, 256, 0, h->stream>>>(a);
+    else k_regfeat_runs<double><<<g, 256, 0, h->stream>>>(a);
+    LAUNCHCHK();
+    record(h, 2);
+    // the largest id: the sort's bits, and the 2^53 limit of the id column
+    unsigned long long vmax = 0;
+    HIPCHK(hipMemcpyAsync(&vmax, red + 16, sizeof(vmax), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (vmax >= (1ull << 53)) {
+        h->err = "region features: an id of 2^53 or more (" + std::to_string(vmax) +
+                 ") has no exact place in the float64 rows";
+        return CTWS_EUNSUPPORTED;
+    }
+    int bits = 1;
+    while (bits < 53 && (1ull << bits) <= vmax) ++bits;
+    size_t tb_sort = 0, tb_rle = 0;
+    HIPCHK(pair_sort(nullptr, tb_sort, nullptr, nullptr, nullptr, nullptr, n, bits, h->stream));
+    HIPCHK(u64_runs(nullptr, tb_rle, nullptr, nullptr, nullptr, nullptr, n, h->stream));
+    if ((r = grow(h, h->rg_skeys, nb)) != CTWS_OK) return r;
+    if ((r = grow(h, h->rg_sw, nb)) != CTWS_OK) return r;
+    if ((r = grow(h, h->rg_keys, nb)) != CTWS_OK) return r;
+    if ((r = grow(h, h->rg_sum, nb)) != CTWS_OK) return r;
+    if ((r = grow(h, h->rg_tmp, std::max(tb_sort, tb_rle))) != CTWS_OK) return r;
+    uint64_t* sids = (uint64_t*)h->rg_skeys.p;
+    uint64_t* svals = (uint64_t*)h->rg_sw.p;
+    uint64_t* uniq = (uint64_t*)h->rg_keys.p;
+    uint64_t* counts = (uint64_t*)h->rg_sum.p;
+    HIPCHK(pair_sort(h->rg_tmp.p, tb_sort, a.ids, sids, a.vals, svals, n, bits, h->stream));
+    HIPCHK(u64_runs(h->rg_tmp.p, tb_rle, sids, uniq, counts, (uint64_t*)(red + 19), n, h->stream));
+    record(h, 3);
+    unsigned long long runs = 0;
+    HIPCHK(hipMemcpyAsync(&runs, red + 19, sizeof(runs), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    rag_time(h, "regfeat_count", 0, 1);
+    rag_time(h, "regfeat_runs", 1, 2);
+    rag_time(h, "regfeat_sort", 2, 3);
+    add_timing(h, "regfeat_records", (float)total);  // (a count, as the flood's rounds)
+    if (runs == 0 || runs > (unsigned long long)n) {
+        h->err = "region features: " + std::to_string(runs) + " ids from " + std::to_string(n) + " runs";
+        return CTWS_EHIP;
+    }
+    const int64_t m = (int64_t)runs;
+    *n_rows = m;
+    if (m > cap) {
+        h->err = "region features: output capacity too small";
+        return CTWS_EINVAL;
+    }
+    const size_t rb = 3 * sizeof(double) * (size_t)m;
+    double* drows = rows;
+    if (!dev) {
+        if ((r = grow(h, h->rf_rows, rb)) != CTWS_OK) return r;
+        drows = (double*)h->rf_rows.p;
+    }
+    // the chunk table: (n, sum) per whole aligned chunk of sorted records, the n first
+    const int64_t chunks = n / kRegfeatChunk;
+    if ((r = grow(h, h->rf_ctab, 2 * sizeof(uint64_t) * (size_t)std::max<int64_t>(1, chunks))) != CTWS_OK) return r;
+    uint64_t* chunk_n = (uint64_t*)h->rf_ctab.p;
+    double* chunk_s = (double*)(chunk_n + std::max<int64_t>(1, chunks));
+    if (chunks > 0) {
+        const unsigned gc = (unsigned)std::min<int64_t>((chunks + 3) / 4, 2048);
+        k_regfeat_chunks<<<gc, 256, 0, h->stream>>>(sids, svals, a.sums, total, chunk_n, chunk_s);
+        LAUNCHCHK();
+    }
+    const unsigned gm = (unsigned)std::max<int64_t>(1, std::min<int64_t>((m + 3) / 4, 2048));
+    k_regfeat_rows<<<gm, 256, 0, h->stream>>>(sids, svals, a.sums, total, uniq, counts, (uint32_t)m, chunk_n, chunk_s,
+                                              drows);
+    LAUNCHCHK();
+    record(h, 4);
+    if (!dev) HIPCHK(hipMemcpyAsync(rows, drows, rb, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    rag_time(h, "regfeat_rows", 3, 4);
+    return CTWS_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int ctws_region_features_block(ctws_handle* h, const uint64_t* labels, const void* data, int data_dtype, int64_t nz,
+                               int64_t ny, int64_t nx, int with_ignore, uint64_t ignore_label, double* rows,
+                               int64_t cap, int64_t* n_rows) {
+    return region_features_block(h, labels, data, data_dtype, nz, ny, nx, with_ignore, ignore_label, rows, cap,
+                                 n_rows, false);
+}
+
+int ctws_region_features_block_device(ctws_handle* h, const uint64_t* labels, const void* data, int data_dtype,
+                                      int64_t nz, int64_t ny, int64_t nx, int with_ignore, uint64_t ignore_label,
+                                      double* rows, int64_t cap, int64_t* n_rows) {
+    return region_features_block(h, labels, data, data_dtype, nz, ny, nx, with_ignore, ignore_label, rows, cap,
+                                 n_rows, true);
 }
 
 // ---- EdgeFeaturesWorkflow: boundary-map statistics per edge (k_edgefeat.hip) ----------------

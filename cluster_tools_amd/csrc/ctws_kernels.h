@@ -352,6 +352,32 @@ constexpr int kMorphChunk = 2048;
 __global__ void k_morph_rows(const uint64_t*, const uint64_t*, uint32_t, const uint64_t*, const uint64_t*, uint32_t,
                              MorphBegin, unsigned long long*, double*);
 __global__ void k_morph_long_rows(const uint64_t*, uint32_t, MorphBegin, const unsigned long long*, double*);
+// k_regfeat.hip (RegionFeaturesWorkflow: the runs of equal ids along x with the sum of their values,
+// placed by a scan of the rows' run counts, then one [id, n, mean] row per id)
+struct RegfeatArgs {
+    const uint64_t* lab;        // the block's labels, rows x nx
+    const void* data;           // the input map on the same box (the kernel's template type)
+    uint32_t rows, nx;          // rows = nz * ny, rows * nx < 2^31
+    int with_ignore;            // runs of ignore get length 0 and sum 0
+    uint64_t ignore;
+    const uint32_t* row_first;  // the exclusive scan of k_regfeat_count's row counts
+    uint32_t n;                 // the number of records: the scan's total
+    uint64_t* ids;              // out: the run's id per record
+    uint64_t* vals;             // out: run length << 32 | record index
+    double* sums;               // out: the float64 sum of the run's float32 values
+    unsigned long long* vmax;   // the largest id of the block (atomicMax; zeroed)
+};
+__global__ void k_regfeat_count(const uint64_t*, uint32_t, uint32_t, uint32_t*);
+template <class T>
+__global__ void k_regfeat_runs(RegfeatArgs);
+// sorted records per chunk: an id's segment that holds whole aligned chunks gives them to one wave
+// each (k_regfeat_chunks), as k_morph_rows does
+constexpr int kRegfeatChunk = kMorphChunk;
+__global__ void k_regfeat_chunks(const uint64_t*, const uint64_t*, const double*, uint32_t, uint64_t*, double*);
+__global__ void k_regfeat_rows(const uint64_t*, const uint64_t*, const double*, uint32_t, const uint64_t*,
+                               const uint64_t*, uint32_t, const uint64_t*, const double*, double*);
+hipError_t u32_exclusive_sum(void* tmp, size_t& bytes, const uint32_t* in, uint32_t* out, int64_t n,
+                             hipStream_t stream);
 // k_edgefeat.hip (EdgeFeaturesWorkflow: the boundary-map statistics of a block's edges)
 struct EfArgs {
     const uint64_t* lab;          // the block's labels, (nz, ny, nx): the extended box

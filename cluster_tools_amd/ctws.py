@@ -76,6 +76,10 @@ def lib():
             for fn in ('ctws_block_morphology', 'ctws_block_morphology_device'):
                 getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                            C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+            for fn in ('ctws_region_features_block', 'ctws_region_features_block_device'):
+                getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64,
+                                           C.c_int64, C.c_int, C.c_uint64, C.c_void_p, C.c_int64,
+                                           C.POINTER(C.c_int64)]
             for fn in ('ctws_edge_features_block', 'ctws_edge_features_block_device'):
                 getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_int64] * 6 + [
                     C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]
@@ -105,7 +109,8 @@ EXPORTED_SYMBOLS = ('ctws_abi_version', 'ctws_open', 'ctws_close', 'ctws_last_er
                     'ctws_threshold_components_ex', 'ctws_ufd_find', 'ctws_set_discard_u64', 'ctws_size_filter_blocks',
                     'ctws_size_filter_blocks_device', 'ctws_unique_pairs_u64', 'ctws_rag_block', 'ctws_rag_block_device',
                     'ctws_edge_features_block', 'ctws_edge_features_block_device', 'ctws_label_overlaps',
-                    'ctws_label_overlaps_device', 'ctws_block_morphology', 'ctws_block_morphology_device')
+                    'ctws_label_overlaps_device', 'ctws_block_morphology', 'ctws_block_morphology_device',
+                    'ctws_region_features_block', 'ctws_region_features_block_device')
 
 
 def ufd_find(n_labels, pairs):
@@ -863,6 +868,80 @@ class Handle:
                 break
             cap = n.value
         self._check(ret, 'ctws_block_morphology_device')
+        return rows[:n.value]
+
+    # ---- RegionFeaturesWorkflow kernels ----------------------------------------------------
+    # first capacity of region_features_block in rows: a call that does not fit computes everything again
+    REGION_FEATURES_CAP = 1 << 16
+    REGION_FEATURES_DTYPES = ('uint8', 'uint16', 'float32', 'float64')
+
+    def region_features_block_raw(self, labels, data, ignore_label, cap):
+        """One ctws_region_features_block call with an output of `cap` rows: (return code, n_rows,
+        rows (cap, 3)).  labels is a 3-D uint64 array, data of the same shape (refused as
+        region_features_block refuses them); the rows start out as NaN, so a call that writes
+        nothing leaves them so."""
+        labels = np.asarray(labels)
+        data = np.asarray(data)
+        self._region_features_check(labels.dtype, labels.shape, data.dtype, data.shape)
+        labels = np.ascontiguousarray(labels)
+        data = np.ascontiguousarray(data)
+        rows = np.full((cap, 3), np.nan, dtype=np.float64)
+        n = C.c_int64(0)
+        wi, il = self._ignore_args(ignore_label)
+        ret = lib().ctws_region_features_block(self._h, labels.ctypes.data, data.ctypes.data, dtype_code(data.dtype),
+                                               *labels.shape, wi, il, rows.ctypes.data if cap else None, cap,
+                                               C.byref(n))
+        return ret, int(n.value), rows
+
+    @classmethod
+    def _region_features_check(cls, l_dtype, l_shape, d_dtype, d_shape):
+        if str(l_dtype).replace('torch.', '') != 'uint64':
+            raise TypeError("region features: the labels are uint64, not %s" % (l_dtype,))
+        if str(d_dtype).replace('torch.', '') not in cls.REGION_FEATURES_DTYPES:
+            raise TypeError("region features: the input map is uint8, uint16, float32 or float64, not %s"
+                            % (d_dtype,))
+        l_shape, d_shape = tuple(l_shape), tuple(d_shape)
+        if l_shape != d_shape:
+            raise ValueError("region features: labels and input map are of one shape, not %s and %s"
+                             % (l_shape, d_shape))
+        if len(l_shape) != 3 or 0 in l_shape:
+            raise ValueError("region features: the labels are a non-empty 3-D block, not %s" % (l_shape,))
+
+    def region_features_block(self, labels, data, ignore_label=0):
+        """The region features of one block (include/ctws.h, ctws_region_features_block): labels
+        (uint64) and data (uint8 taken as v / 255, uint16, float32 or float64, all as float32) of one
+        3-D shape -> rows (m, 3) float64 of [id, count, mean], a row per id of the block, sorted by
+        id.  ignore_label not None: that id's row, if it occurs, is [id, 0, 0].  A call that hits
+        the capacity is repeated once with the returned size."""
+        cap = self.REGION_FEATURES_CAP
+        ret, m, rows = self.region_features_block_raw(labels, data, ignore_label, cap)
+        if ret == -1 and m > cap:
+            ret, m, rows = self.region_features_block_raw(labels, data, ignore_label, m)
+        self._check(ret, 'ctws_region_features_block')
+        return rows[:m]
+
+    def region_features_block_device(self, labels, data, ignore_label=0):
+        """region_features_block on torch tensors on this GPU: labels uint64 / int64 (the bits are
+        taken as uint64), data uint8, uint16, float32 or float64; the rows come back as a float64
+        tensor on the same device: only their number crosses PCIe."""
+        import torch
+        for t in (labels, data):
+            assert t.is_cuda and t.is_contiguous()
+        l_dtype = 'uint64' if labels.element_size() == 8 and not labels.is_floating_point() else labels.dtype
+        self._region_features_check(l_dtype, labels.shape, data.dtype, data.shape)
+        code = dtype_code(np.dtype(str(data.dtype).replace('torch.', '')))
+        torch.cuda.current_stream(labels.device).synchronize()
+        wi, il = self._ignore_args(ignore_label)
+        n = C.c_int64(0)
+        cap = self.REGION_FEATURES_CAP
+        for _ in range(2):
+            rows = torch.empty((cap, 3), dtype=torch.float64, device=labels.device)
+            ret = lib().ctws_region_features_block_device(self._h, labels.data_ptr(), data.data_ptr(), code,
+                                                          *labels.shape, wi, il, rows.data_ptr(), cap, C.byref(n))
+            if not (ret == -1 and n.value > cap):
+                break
+            cap = n.value
+        self._check(ret, 'ctws_region_features_block_device')
         return rows[:n.value]
 
     # ---- multi-GPU label-count exchange (RCCL) ------------------------------------------

@@ -1,1 +1,1 @@
-from .features_workflow import EdgeFeaturesWorkflow  # noqa: F401
+from .features_workflow import EdgeFeaturesWorkflow, RegionFeaturesWorkflow  # noqa: F401

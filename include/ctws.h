@@ -358,6 +358,39 @@ int ctws_block_morphology_device(ctws_handle* h, const uint64_t* labels, int64_t
                                  const int64_t begin[3], double* rows, int64_t cap, int64_t* n_rows);
 
 /*
+ * RegionFeaturesWorkflow (features/features_workflow.py:71-112), RegionFeatures: the number of
+ * voxels and the mean input value of every id of a block (region_features.py:122-167,
+ * `vigra.analysis.extractRegionFeatures(..., ['mean', 'count'], ignoreLabel=...)` on
+ * `vu.normalize(input)`, restated: DESIGN.md section 3.8).
+ *
+ * ctws_region_features_block / _device: labels (uint64) and data (data_dtype CTWS_U8 / U16 / F32 /
+ *   F64) are one block, shape (nz, ny, nx), C order.  The value of a voxel is float32: uint8 gives
+ *   float32(v) / 255.0f, uint16 and float32 give float32(v) (uint16 is not scaled), float64 is
+ *   rounded to nearest.  NaN values are not supported (an id that holds one gets a NaN mean).
+ *     rows    m x 3 float64, C order, a row per id that occurs in the block, sorted by id:
+ *             [id, n, mean], n = the id's number of voxels, mean = float64(sum) / float64(n) with
+ *             one IEEE division, sum = the float64 sum of the id's float32 values.  With
+ *             with_ignore != 0 the row of ignore_label, if that id occurs, is [ignore_label, 0, 0];
+ *             a block that holds nothing else gives that single row (the rule that skips such a
+ *             block is the task's).
+ *   *n_rows is always set; CTWS_EINVAL when cap (in rows) is too small (nothing written: retry
+ *   with that size) or data_dtype is none of the four.  Ids below 2^53 (the id column is exact)
+ *   and fewer than 2^31 voxels in fewer than 2^31 - 1 rows (nz * ny): CTWS_EUNSUPPORTED
+ *   otherwise, never a wrong row.  The sum of an id is taken in an order that follows from the labels alone -- no floating-point atomic, no
+ *   dependence on the order in which waves run -- so the rows depend on the inputs alone: repeated
+ *   calls, and the host- and device-pointer forms, agree byte for byte.  Its error against the
+ *   exact sum is that of a float64 sum of n terms in some order, at most (n - 1) 2^-53 sum|x|.
+ *   Host pointers are staged through HBM; _device takes device pointers on the handle's GPU for
+ *   labels, data and rows.
+ */
+int ctws_region_features_block(ctws_handle* h, const uint64_t* labels, const void* data, int data_dtype, int64_t nz,
+                               int64_t ny, int64_t nx, int with_ignore, uint64_t ignore_label, double* rows,
+                               int64_t cap, int64_t* n_rows);
+int ctws_region_features_block_device(ctws_handle* h, const uint64_t* labels, const void* data, int data_dtype,
+                                      int64_t nz, int64_t ny, int64_t nx, int with_ignore, uint64_t ignore_label,
+                                      double* rows, int64_t cap, int64_t* n_rows);
+
+/*
  * EdgeFeaturesWorkflow (features/features_workflow.py:14-66), BlockEdgeFeatures: the boundary-map
  * statistics of the edges of one block (block_edge_features.py:113-132,
  * `ndist.extractBlockFeaturesFromBoundaryMaps_*`, restated: DESIGN.md section 3.5).
