@@ -378,6 +378,25 @@ __global__ void k_regfeat_rows(const uint64_t*, const uint64_t*, const double*, 
                                const uint64_t*, uint32_t, const uint64_t*, const double*, double*);
 hipError_t u32_exclusive_sum(void* tmp, size_t& bytes, const uint32_t* in, uint32_t* out, int64_t n,
                              hipStream_t stream);
+// k_downscale.hip (DownscalingWorkflow: mean / max / min over fz x fy x fx cells, zero-padded ends)
+constexpr int kDsMean = 0, kDsMax = 1, kDsMin = 2;
+struct DownscaleArgs {
+    const void* in;          // the block (nz, ny, nx) of the kernel's template type
+    void* out;               // (oz, oy, ox) = ceil(n / f) per axis, same type
+    uint32_t nz, ny, nx;     // nz * ny * nx < 2^31
+    uint32_t oz, oy, ox;
+    uint32_t fz, fy, fx;     // 1..8 each (k_downscale_vec: FZ, 2, 2)
+    uint32_t groups, per;    // k_downscale_vec: 16-byte output groups per row, work items per row
+    uint32_t items;          // the work items of the launch
+    uint32_t* flag;          // the flag table (zeroed by the caller): a slot |= 1 when a voxel is nonzero
+};
+// the any-nonzero flag is kDsFlagSlots words, kDsFlagStride words (a cache line) apart, a slot per
+// workgroup index modulo kDsFlagSlots: the block holds a nonzero voxel when any slot is set
+constexpr int kDsFlagSlots = 128, kDsFlagStride = 32;
+template <class T, int FUNC>
+__global__ void k_downscale_cell(DownscaleArgs);
+template <class T, int FUNC, int FZ>
+__global__ void k_downscale_vec(DownscaleArgs);
 // k_edgefeat.hip (EdgeFeaturesWorkflow: the boundary-map statistics of a block's edges)
 struct EfArgs {
     const uint64_t* lab;          // the block's labels, (nz, ny, nx): the extended box

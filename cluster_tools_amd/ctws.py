@@ -80,6 +80,10 @@ def lib():
                 getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64,
                                            C.c_int64, C.c_int, C.c_uint64, C.c_void_p, C.c_int64,
                                            C.POINTER(C.c_int64)]
+            for fn in ('ctws_downscale_block', 'ctws_downscale_block_device'):
+                getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64,
+                                           C.POINTER(C.c_int64), C.c_int, C.c_void_p, C.c_int64, C.c_int64,
+                                           C.c_int64, C.POINTER(C.c_int)]
             for fn in ('ctws_edge_features_block', 'ctws_edge_features_block_device'):
                 getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_int64] * 6 + [
                     C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]
@@ -110,7 +114,8 @@ EXPORTED_SYMBOLS = ('ctws_abi_version', 'ctws_open', 'ctws_close', 'ctws_last_er
                     'ctws_size_filter_blocks_device', 'ctws_unique_pairs_u64', 'ctws_rag_block', 'ctws_rag_block_device',
                     'ctws_edge_features_block', 'ctws_edge_features_block_device', 'ctws_label_overlaps',
                     'ctws_label_overlaps_device', 'ctws_block_morphology', 'ctws_block_morphology_device',
-                    'ctws_region_features_block', 'ctws_region_features_block_device')
+                    'ctws_region_features_block', 'ctws_region_features_block_device', 'ctws_downscale_block',
+                    'ctws_downscale_block_device')
 
 
 def ufd_find(n_labels, pairs):
@@ -943,5 +948,66 @@ class Handle:
             cap = n.value
         self._check(ret, 'ctws_region_features_block_device')
         return rows[:n.value]
+
+    # ---- DownscalingWorkflow kernel ---------------------------------------------------------
+    DOWNSCALE_DTYPES = ('uint8', 'uint16', 'float32', 'float64')
+    DOWNSCALE_FUNCS = {'mean': 0, 'max': 1, 'min': 2}
+
+    @classmethod
+    def _downscale_check(cls, dtype, shape, factors, func):
+        """The Python-side refusals of downscale_block: -> (factors, func code, output shape)."""
+        if str(dtype).replace('torch.', '') not in cls.DOWNSCALE_DTYPES:
+            raise TypeError("downscale: the block is uint8, uint16, float32 or float64, not %s" % (dtype,))
+        shape = tuple(int(s) for s in shape)
+        if len(shape) != 3 or 0 in shape:
+            raise ValueError("downscale: the input is a non-empty 3-D block, not %s" % (shape,))
+        try:
+            fac = tuple(int(f) for f in factors)
+            whole = all(f == g for f, g in zip(fac, factors))
+        except TypeError:
+            raise ValueError("downscale: factors are three integers in 1..8, not %r" % (factors,))
+        if len(fac) != 3 or not whole or any(f < 1 or f > 8 for f in fac):
+            raise ValueError("downscale: factors are three integers in 1..8, not %r" % (factors,))
+        if func not in cls.DOWNSCALE_FUNCS:
+            raise ValueError("downscale: func is 'mean', 'max' or 'min', not %r" % (func,))
+        return fac, cls.DOWNSCALE_FUNCS[func], tuple(-(-s // f) for s, f in zip(shape, fac))
+
+    def downscale_block_raw(self, x, factors, func, out):
+        """One ctws_downscale_block call into `out` (a C-contiguous array of x's dtype): (return
+        code, any_nonzero).  Nothing is refused here: the library's own checks answer."""
+        x = np.ascontiguousarray(x)
+        flag = C.c_int(-1)
+        ret = lib().ctws_downscale_block(self._h, x.ctypes.data, dtype_code(x.dtype), *x.shape,
+                                         (C.c_int64 * 3)(*[int(f) for f in factors]), int(func), out.ctypes.data,
+                                         *out.shape, C.byref(flag))
+        return ret, int(flag.value)
+
+    def downscale_block(self, x, factors, func='mean'):
+        """One block of a scale pyramid (include/ctws.h, ctws_downscale_block): x (nz, ny, nx) of
+        uint8, uint16, float32 or float64, factors (fz, fy, fx) in 1..8, func 'mean', 'max' or 'min'
+        -> (out, any_nonzero): out of shape ceil(n / f) per axis in x's dtype, as
+        `skimage.measure.block_reduce` of the float32 block, clipped, rounded and cast; any_nonzero
+        False when every voxel of x is zero."""
+        x = np.asarray(x)
+        fac, code, oshape = self._downscale_check(x.dtype, x.shape, factors, func)
+        out = np.empty(oshape, dtype=x.dtype)
+        ret, flag = self.downscale_block_raw(x, fac, code, out)
+        self._check(ret, 'ctws_downscale_block')
+        return out, bool(flag)
+
+    def downscale_block_device(self, x, factors, func='mean'):
+        """downscale_block on a torch tensor on this GPU; out comes back as a tensor of the same
+        dtype on the same device: only the flag crosses PCIe."""
+        import torch
+        assert x.is_cuda and x.is_contiguous()
+        fac, code, oshape = self._downscale_check(x.dtype, x.shape, factors, func)
+        dcode = dtype_code(np.dtype(str(x.dtype).replace('torch.', '')))
+        torch.cuda.current_stream(x.device).synchronize()
+        out = torch.empty(oshape, dtype=x.dtype, device=x.device)
+        flag = C.c_int(-1)
+        ret = lib().ctws_downscale_block_device(self._h, x.data_ptr(), dcode, *x.shape, (C.c_int64 * 3)(*fac), code,
+                                                out.data_ptr(), *oshape, C.byref(flag))
+        self._check(ret, 'ctws_downscale_block_device')
+        return out, bool(flag.value)
 
     # ---- multi-GPU label-count exchange (RCCL) ------------------------------------------

@@ -1,0 +1,272 @@
+#! /usr/bin/env python
+"""Downscaling: one level of a scale pyramid by block reduction on the GPU
+(cluster_tools/downscaling/downscaling.py:31-393; task surface, parameters, config keys, job config
+keys, the per-prefix job and log names and the log lines unchanged).  The job replaces
+`skimage.measure.block_reduce` of the float32 block and the clip / round / cast behind it
+(:222-229, :309-310) by `Handle.downscale_block`: one library handle per job, the input boxes read
+ahead on a thread.  Per block it reads what the reference reads -- the outer block (the block and
+its downscaled halo) in output coordinates, times the factor, clipped to the input -- skips an
+all-zero box (the kernel's any-nonzero flag) and writes the crop to the inner block.
+
+Two things are refused, never guessed:
+* `library: 'vigra'` (the default of the task config, kept as the reference's):
+  `vigra.sampling.resize` is not restated -- its resampling grid and spline prefilter are recorded
+  nowhere here -- so the task raises NotImplementedError and asks for `library: 'skimage'`.  With
+  that, a dtype outside float32 / float64 / uint8 / uint16 keeps the reference's assertion
+  (labels need vigra's order 0).
+* a block whose reduced box is smaller than its output box: `downsample_shape` makes the output
+  longer than ceil(n / f) for a factor >= 3 on an extent it does not divide; the reference dies
+  there in the write, here the job raises a ValueError that names the block and both shapes."""
+import json
+import os
+import sys
+from concurrent import futures
+
+import numpy as np
+
+from cluster_tools_amd import luigi_compat as luigi
+import cluster_tools_amd.utils.volume_utils as vu
+import cluster_tools_amd.utils.function_utils as fu
+from cluster_tools_amd.utils.blocking import Blocking
+from cluster_tools_amd.cluster_tasks import SlurmTask, LocalTask, LSFTask
+from cluster_tools_amd.utils.task_utils import DummyTask
+
+FUNCTIONS = ('mean', 'max', 'min')
+
+
+def check_library(library, library_kwargs):
+    """The sampler a config asks for: -> the reduction's name, or the refusal."""
+    assert library in ('vigra', 'skimage'), "Downscaling is only supported with vigra or skimage"
+    if library == 'vigra':
+        raise NotImplementedError("downscaling: library 'vigra' is not available: vigra.sampling.resize is not "
+                                  "restated (its resampling grid and spline prefilter are not recorded); "
+                                  "set library: 'skimage' (block reduction on the GPU)")
+    function = (library_kwargs or {}).get('function', 'mean')
+    if function not in FUNCTIONS:
+        raise NotImplementedError("downscaling: library_kwargs['function'] = %r: the block reduction is 'mean', "
+                                  "'max' or 'min'" % (function,))
+    return function
+
+
+class DownscalingBase(luigi.Task):
+    task_name = 'downscaling'
+    src_file = os.path.abspath(__file__)
+
+    input_path = luigi.Parameter()
+    input_key = luigi.Parameter()
+    output_path = luigi.Parameter()
+    output_key = luigi.Parameter()
+    # an int, or [fz, fy, fx] for anisotropic downscaling
+    scale_factor = luigi.Parameter()
+    # makes the task, its jobs and its logs unique per level
+    scale_prefix = luigi.Parameter()
+    halo = luigi.ListParameter(default=[])
+    effective_scale_factor = luigi.ListParameter(default=[])
+    dependency = luigi.TaskParameter(default=DummyTask())
+
+    interpolatable_types = ('float32', 'float64', 'uint8', 'uint16')
+
+    def requires(self):
+        return self.dependency
+
+    @staticmethod
+    def default_task_config():
+        config = LocalTask.default_task_config()
+        config.update({'library': 'vigra', 'chunks': None, 'compression': 'gzip', 'library_kwargs': None})
+        return config
+
+    def downsample_shape(self, shape):
+        """The reference's output shape (downscaling.py:69-80), as it stands: a non-divisible
+        extent n gives n // f + (f - n % f), which is ceil(n / f) only for f = 2."""
+        spatial = shape[1:] if len(shape) == 4 else shape
+        if isinstance(self.scale_factor, (list, tuple)):
+            factors = self.scale_factor
+        else:
+            factors = (self.scale_factor,) * len(spatial)
+        return tuple(sh // sf if sh % sf == 0 else sh // sf + (sf - sh % sf) for sh, sf in zip(spatial, factors))
+
+    def _scale_factor(self):
+        """An int, three equal values collapsed to an int, or [1, k, k]."""
+        sf = self.scale_factor
+        if isinstance(sf, int):
+            return sf
+        assert len(sf) == 3
+        if all(s == sf[0] for s in sf):
+            return sf[0]
+        # anisotropic downscaling is in-plane only
+        assert sf[0] == 1
+        assert sf[1] == sf[2]
+        return list(sf)
+
+    def _scaled_roi(self, roi_begin, roi_end, scale_factor, shape):
+        effective = self.effective_scale_factor if self.effective_scale_factor else scale_factor
+        self._write_log("downscaling roi with effective scale %s" % str(effective))
+        self._write_log("ROI before scaling: %s to %s" % (str(roi_begin), str(roi_end)))
+        effective = [effective] * 3 if isinstance(effective, int) else list(effective)
+        roi_begin = [rb // sf for rb, sf in zip(roi_begin, effective)]
+        roi_end = [sh if re is None else re // sf for re, sf, sh in zip(roi_end, effective, shape)]
+        self._write_log("ROI after scaling: %s to %s" % (str(roi_begin), str(roi_end)))
+        return roi_begin, roi_end
+
+    def run_impl(self):
+        shebang, block_shape, roi_begin, roi_end, block_list_path = self.global_config_values(True)
+        self.init(shebang)
+
+        task_config = self.get_task_config()
+        library = task_config.get('library', 'vigra')
+        # the refusals come before any path is opened and before any job config is written
+        check_library(library, task_config.get('library_kwargs'))
+
+        with vu.file_reader(self.input_path, 'r') as f:
+            prev_shape = tuple(f[self.input_key].shape)
+            dtype = f[self.input_key].dtype
+        assert len(prev_shape) in (3, 4), "Only support 3d or 4d inputs"
+        assert str(dtype) in self.interpolatable_types, \
+            "datatype %s is not interpolatable, set library to vigra" % dtype
+
+        shape = self.downsample_shape(prev_shape)
+        self._write_log('downscaling with factor %s from shape %s to %s' % (str(self.scale_factor), str(prev_shape),
+                                                                            str(shape)))
+        scale_factor = self._scale_factor()
+
+        chunks = task_config.pop('chunks', None)
+        if chunks is None:
+            chunks = tuple(bs // 2 for bs in block_shape)
+        else:
+            chunks = tuple(chunks)
+            assert len(chunks) == 3, "Chunks must be 3d"
+        chunks = tuple(min(ch, sh) for sh, ch in zip(shape, chunks))
+        if len(prev_shape) == 4:
+            out_shape, out_chunks = (prev_shape[0],) + shape, (1,) + chunks
+        else:
+            out_shape, out_chunks = shape, chunks
+
+        compression = task_config.pop('compression', 'gzip')
+        with vu.file_reader(self.output_path) as f:
+            f.require_dataset(self.output_key, shape=out_shape, chunks=out_chunks, compression=compression,
+                              dtype=dtype)
+
+        task_config.update({'input_path': self.input_path, 'input_key': self.input_key,
+                            'output_path': self.output_path, 'output_key': self.output_key,
+                            'block_shape': block_shape, 'scale_factor': scale_factor,
+                            'halo': list(self.halo) if self.halo else None})
+
+        if roi_begin is not None:
+            assert roi_end is not None
+            roi_begin, roi_end = self._scaled_roi(roi_begin, roi_end, scale_factor, shape)
+
+        if self.n_retries == 0:
+            block_list = vu.blocks_in_volume(shape, block_shape, roi_begin, roi_end, block_list_path)
+            self._write_log("scheduled %i blocks to run" % len(block_list))
+        else:
+            block_list = self.block_list
+            self.clean_up_for_retry(block_list)
+
+        n_jobs = min(len(block_list), self.max_jobs)
+        self.prepare_jobs(n_jobs, block_list, task_config, self.scale_prefix)
+        self.submit_jobs(n_jobs, self.scale_prefix)
+        self.wait_for_jobs(self.scale_prefix)
+        self.check_jobs(n_jobs, self.scale_prefix)
+
+    def output(self):
+        return luigi.LocalTarget(os.path.join(self.tmp_folder, self.task_name + '_%s.log' % self.scale_prefix))
+
+
+class DownscalingLocal(DownscalingBase, LocalTask):
+    pass
+
+
+class DownscalingSlurm(DownscalingBase, SlurmTask):
+    pass
+
+
+class DownscalingLSF(DownscalingBase, LSFTask):
+    pass
+
+
+#
+# Implementation
+#
+
+def _device():
+    return int(os.environ.get('CTWS_DEVICE', os.environ.get('LOCAL_RANK', '0')))
+
+
+def block_boxes(blocking, block_id, factors, halo, in_shape):
+    """The boxes of one block (downscaling.py:232-263): the input box (the outer block in output
+    coordinates, times the factor, clipped to the input), the output box (the inner block), the
+    inner block inside the outer one.  A box that does not reduce to the outer block's shape is a
+    ValueError."""
+    if halo is None:
+        block = blocking.getBlock(block_id)
+        outer = inner = block
+        local_bb = tuple(slice(0, s) for s in block.shape)
+    else:
+        halo_ds = [ha // sf for sf, ha in zip(factors, halo)]
+        block = blocking.getBlockWithHalo(block_id, halo_ds)
+        outer, inner = block.outerBlock, block.innerBlock
+        local_bb = vu.block_to_bb(block.innerBlockLocal)
+    in_bb = tuple(slice(b * sf, min(e * sf, sh)) for b, e, sf, sh in zip(outer.begin, outer.end, factors, in_shape))
+    box = tuple(s.stop - s.start for s in in_bb)
+    reduced = tuple(-(-n // sf) for n, sf in zip(box, factors))
+    if reduced != tuple(outer.shape):
+        raise ValueError("downscaling: block %i: the input box %s reduces by %s to %s, the block's output box has "
+                         "shape %s (the output extent is no ceil(n / f) of the input's); nothing is padded"
+                         % (block_id, str(box), str(tuple(factors)), str(reduced), str(tuple(outer.shape))))
+    return in_bb, vu.block_to_bb(inner), local_bb
+
+
+def run_downscaling_blocks(blocking, block_list, ds_in, ds_out, factors, halo, function):
+    """Reduce, crop and write every block of the job."""
+    from cluster_tools_amd import ctws
+    with_channels = ds_in.ndim == 4
+    in_shape = tuple(ds_in.shape[1:] if with_channels else ds_in.shape)
+    lead = (slice(None),) if with_channels else ()
+
+    def read(block_id):
+        boxes = block_boxes(blocking, block_id, factors, halo, in_shape)
+        return boxes, ds_in[lead + boxes[0]]
+
+    with ctws.Handle(_device()) as h, futures.ThreadPoolExecutor(1) as io:
+        nxt = io.submit(read, block_list[0]) if block_list else None
+        for k, block_id in enumerate(block_list):
+            fu.log("start processing block %i" % block_id)
+            (in_bb, out_bb, local_bb), x = nxt.result()
+            nxt = io.submit(read, block_list[k + 1]) if k + 1 < len(block_list) else None
+            channels = x if with_channels else x[None]
+            reduced = [h.downscale_block(c, factors, function) for c in channels]
+            # the reference samples nothing when the whole box (every channel) is zero
+            if not any(nonzero for _, nonzero in reduced):
+                fu.log_block_success(block_id)
+                continue
+            out = np.stack([r for r, _ in reduced])
+            out = out[lead + local_bb] if with_channels else out[0][local_bb]
+            ds_out[lead + out_bb] = out
+            fu.log_block_success(block_id)
+
+
+def downscaling(job_id, config_path):
+    fu.log("start processing job %i" % job_id)
+    fu.log("reading config from %s" % config_path)
+    with open(config_path) as f:
+        config = json.load(f)
+    function = check_library(config.get('library', 'vigra'), config.get('library_kwargs'))
+    scale_factor = config['scale_factor']
+    factors = [scale_factor] * 3 if isinstance(scale_factor, int) else list(scale_factor)
+    halo = config.get('halo', None)
+    # one container serves both datasets: the workflow writes every level next to its input
+    f_out = vu.file_reader(config['output_path'])
+    f_in = f_out if config['input_path'] == config['output_path'] else vu.file_reader(config['input_path'], 'r')
+    with f_in, f_out:
+        ds_in, ds_out = f_in[config['input_key']], f_out[config['output_key']]
+        shape = list(ds_out.shape[1:] if ds_out.ndim == 4 else ds_out.shape)
+        blocking = Blocking([0, 0, 0], shape, list(config['block_shape']))
+        run_downscaling_blocks(blocking, config['block_list'], ds_in, ds_out, factors, halo, function)
+    fu.log_job_success(job_id)
+
+
+if __name__ == '__main__':
+    path = sys.argv[1]
+    assert os.path.exists(path), path
+    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
+    downscaling(job_id, path)

@@ -391,6 +391,41 @@ int ctws_region_features_block_device(ctws_handle* h, const uint64_t* labels, co
                                       double* rows, int64_t cap, int64_t* n_rows);
 
 /*
+ * DownscalingWorkflow (downscaling/downscaling_workflow.py:218-347), Downscaling with
+ * `library: 'skimage'`: one block of one level of a scale pyramid (downscaling.py:222-229 `_ds_vol`
+ * over :309-310 `block_reduce`, restated: DESIGN.md section 3.9).
+ *
+ * ctws_downscale_block / _device: input = one block (nz, ny, nx), C order, of dtype CTWS_U8,
+ *   CTWS_U16, CTWS_F32 or CTWS_F64; factors = (fz, fy, fx), each 1..8; func 0 mean, 1 max, 2 min.
+ *   out (oz, oy, ox) = (ceil(nz / fz), ceil(ny / fy), ceil(nx / fx)), C order, in the input's
+ *   dtype; the caller passes the extents, any other is CTWS_EINVAL.
+ *     cell    out[z, y, x] reduces input[z fz .. (z + 1) fz, y fy .., x fx ..]; the input is
+ *             zero-padded at the end of every axis to a multiple of its factor, and the zeros take
+ *             part: the mean divides by n = fz fy fx, a padded cell's min is <= 0, its max >= 0.
+ *     value   float64 is rounded to float32 (to nearest) first; every dtype is reduced as float32
+ *     mean    float32(S) / float32(n), one IEEE float32 division.  Integers: S is the cell's exact
+ *             integer sum; then clip to the dtype's range, round half to even, cast.  A uint16 mean
+ *             with n > 256 (n 65535 >= 2^24: float32 no longer holds S, the reference's float32
+ *             summation order would decide) is CTWS_EUNSUPPORTED.  Floats: S is the float64 sum in
+ *             the order z, then y, then x ascending, rounded once to float32; float64 output is the
+ *             float32 result widened.
+ *     max/min exact.
+ *   *any_nonzero = 0 when every input voxel is zero (-0.0 is zero), else 1: the reference's
+ *   `np.sum(x != 0) == 0` skip test, taken in the same pass.  out is written either way.
+ *   NaN inputs are not supported.  No floating-point atomics: the output depends on the input
+ *   alone, so repeated calls, and the host- and device-pointer forms, agree byte for byte.
+ *   Fewer than 2^31 voxels per block: more is CTWS_EUNSUPPORTED before any memory is touched.
+ *   Host pointers are staged through HBM; _device takes device pointers on the handle's GPU for
+ *   input and out (any_nonzero stays a host pointer).  A 4-D volume is one call per channel.
+ */
+int ctws_downscale_block(ctws_handle* h, const void* input, int dtype, int64_t nz, int64_t ny, int64_t nx,
+                         const int64_t factors[3], int func, void* out, int64_t oz, int64_t oy, int64_t ox,
+                         int* any_nonzero);
+int ctws_downscale_block_device(ctws_handle* h, const void* input, int dtype, int64_t nz, int64_t ny, int64_t nx,
+                                const int64_t factors[3], int func, void* out, int64_t oz, int64_t oy, int64_t ox,
+                                int* any_nonzero);
+
+/*
  * EdgeFeaturesWorkflow (features/features_workflow.py:14-66), BlockEdgeFeatures: the boundary-map
  * statistics of the edges of one block (block_edge_features.py:113-132,
  * `ndist.extractBlockFeaturesFromBoundaryMaps_*`, restated: DESIGN.md section 3.5).
