@@ -76,6 +76,7 @@ struct Workspace {
     uint32_t* wlcnt = nullptr;  // worklist length per iteration
     int64_t cap_fstat = 0;
     uint32_t* fstat = nullptr;  // CTWS_TRACE statistics: open voxels, frontier visits per block
+    uint32_t* sfacc = nullptr;  // k_sf_plan's sums, 4 per block
 };
 
 constexpr int kCounterBytes = 4 * (4 + 4 * kStatSlots);  // flood flag + statistics slots
@@ -167,6 +168,7 @@ struct ctws_handle {
     int force_wide = 0;
     int wide_rerun = 0;
     int sf_sparse = 1;  // CTWS_SF_SPARSE=0: the size filter's regrow initialisation scans every block
+    int fuse_hist = 1;  // CTWS_FUSE_HIST=0: the first flood's check and the label histogram as two kernels
     int verify = 1;      // CTWS_VERIFY: 1 (default) check the flood fixpoint + fallback, 2 fail on a violation (tests), 0 off
     int prep_lds = 0;    // CTWS_PREP_LDS=1: LDS row kernel for the x pass at every row length (tests)
     int plateau_fill = 1;  // CTWS_PLATEAU_FILL=0: masked blocks' plateaus relaxed hop by hop (k_plateau.hip)
@@ -342,6 +344,8 @@ int ensure_workspace(ctws_handle* h, int64_t vox, int64_t words, int64_t chunks,
     if (blocks > w.cap_fstat) {
         ALLOC(fstat, 3 * blocks);
         ALLOC(plev, blocks);
+        ALLOC(sfacc, 4 * blocks);
+        HIPCHK(hipMemsetAsync(w.sfacc, 0, sizeof(uint32_t) * 4 * (size_t)blocks, h->stream));  // (k_sf_plan keeps it zero)
         w.cap_fstat = blocks;
     }
     if (!w.counter) ALLOC(counter, kCounterBytes / 4);
@@ -1481,6 +1485,14 @@ int run_batch(ctws_handle* h, const ctws_cfg* cfg, const Plan& pl, ctws_block* b
     int fallback = 0, fiters = 0, fiters2 = 0;
     // statistics (CTWS_TRACE only): open voxels and frontier visits per block
     uint32_t* fst = h->trace ? w.fstat : nullptr;
+    // 2-D ws, pass 1: the first flood's fixpoint check counts the labels for the size filter as it
+    // reads the keys (k_flood_verify_hist2d).  Every other path counts with k_hist2d / k_hist
+    // below: wide keys, pass 2, WatershedFromSeeds, 3-D ws, a stop after the flood, and a batch
+    // flooded again after a violation (its counts would be stale).
+    uint32_t* const counts = (uint32_t*)w.A;  // (w.A: free from the seed CC to the size filter)
+    const bool fuse_hist = h->fuse_hist && descent && pl.nd_ws == 2 && !pl.pass2 && !pl.from_seeds &&
+                           cfg->size_filter > 0 && h->stop_after != CTWS_STOP_FLOOD;
+    bool counts_ready = false;
     if (descent) {
         // descent pre-pass (k_flood.hip): voxels whose steepest descent reaches a seed are final
         // tile-local descent + pointer jumping (16^3 / 1 x 64 x 64 tiles)
@@ -1547,7 +1559,19 @@ int run_batch(ctws_handle* h, const ctws_cfg* cfg, const Plan& pl, ctws_block* b
         // at kDMax sets BlockStat::dsat: the block runs again on the wide keys).  The kernel
         // always runs; CTWS_VERIFY=0 drops only the violation handling.
         HIPCHK(hipMemsetAsync(w.counter, 0, 40, h->stream));
-        if (pl.nd_ws == 3)
+        if (fuse_hist) {
+            k_hist_zero<<<vg, 256, 0, h->stream>>>(w.desc, w.stat, counts);
+            // LDS bins: the power of two above 1.5 x the labels per slice of the batch's densest
+            // block (a slice with more labels counts with global atomics)
+            int64_t per_slice = 0;
+            for (int i = 0; i < nb; ++i)
+                if (s2[i].active) per_slice = std::max<int64_t>(per_slice, (int64_t)s2[i].n_seeds / std::max(desc[i].Z, 1) + 1);
+            int bins = 512;
+            while (bins < kHist2dBins && bins < per_slice + per_slice / 2) bins *= 2;
+            k_flood_verify_hist2d<<<dim3((unsigned)maxZ * 4, nb), kVerifyHistThreads, sizeof(uint32_t) * (size_t)bins,
+                                    h->stream>>>(w.desc, w.stat, w.hm, w.key, w.fopen, w.sb, counts, w.counter, 4, bins);
+            counts_ready = true;
+        } else if (pl.nd_ws == 3)
             k_flood_verify<3><<<wtg, 256, 0, h->stream>>>(w.desc, w.stat, w.hm, w.key, w.fopen, w.counter);
         else
             k_flood_verify<2><<<wtg, 256, 0, h->stream>>>(w.desc, w.stat, w.hm, w.key, w.fopen, w.counter);
@@ -1566,6 +1590,7 @@ int run_batch(ctws_handle* h, const ctws_cfg* cfg, const Plan& pl, ctws_block* b
             }
             if (h->h_counter[0] && !h->no_fallback) {
                 fallback = 1;
+                counts_ready = false;  // the keys change: the size filter counts again
                 k_flood_reset<<<vg, 256, 0, h->stream>>>(w.desc, w.stat, w.hm, w.lab, cc, w.fseed, w.key, w.cls);
                 LAUNCHCHK();
                 if ((r = run_flood(h, pl.nd_ws, packed, nb, max_tiles, TT, w.hm, false, &rounds1, &fk1)) != CTWS_OK)
@@ -1613,7 +1638,6 @@ int run_batch(ctws_handle* h, const ctws_cfg* cfg, const Plan& pl, ctws_block* b
     int n_sf_sparse = 0, n_sf_redo = 0;  // blocks whose removed segments were walked / walked, then scanned
     bool regrow_bad = false;  // the regrow's fixpoint check failed: the batch's blocks fail
     if (cfg->size_filter > 0) {
-        uint32_t* counts = (uint32_t*)w.A;
         auto histogram = [&]() -> int {
             k_hist_zero<<<vg, 256, 0, h->stream>>>(w.desc, w.stat, counts);
             if (pl.nd_ws == 2) {
@@ -1632,7 +1656,7 @@ int run_batch(ctws_handle* h, const ctws_cfg* cfg, const Plan& pl, ctws_block* b
             LAUNCHCHK();
             return CTWS_OK;
         };
-        if ((r = histogram()) != CTWS_OK) return r;
+        if (!counts_ready && (r = histogram()) != CTWS_OK) return r;
         if (packed) {
             // survivors -> regrow seeds, removed voxels -> open; then the frontier relaxation
             std::vector<BlockStat> s3(nb);
@@ -1647,8 +1671,9 @@ int run_batch(ctws_handle* h, const ctws_cfg* cfg, const Plan& pl, ctws_block* b
             auto regrow_init = [&]() -> int {
                 HIPCHK(hipMemsetAsync(w.surv, 0, sizeof(uint32_t) * TS, h->stream));
                 if (sparse_ok) {
-                    k_sf_plan<<<nb, 256, 0, h->stream>>>(w.desc, w.stat, (uint32_t)cfg->size_filter, counts, excl,
-                                                         w.sb, w.surv);
+                    const unsigned split = std::min<unsigned>(kSfPlanSplit, max_seeds / kSfPlanLabels + 1);
+                    k_sf_plan<<<dim3(split, nb), 256, 0, h->stream>>>(
+                        w.desc, w.stat, (uint32_t)cfg->size_filter, counts, excl, w.sb, w.surv, w.sfacc);
                     HIPCHK(hipMemsetAsync(w.fopen, 0, sizeof(uint64_t) * (size_t)TF, h->stream));
                     HIPCHK(hipMemsetAsync(w.front0, 0, sizeof(uint64_t) * (size_t)TF, h->stream));
                     k_sf_sparse<<<dim3((unsigned)std::max<uint32_t>((max_seeds + 255) / 256, 1u), nb), 256, 0,
@@ -1880,6 +1905,7 @@ int run_batch(ctws_handle* h, const ctws_cfg* cfg, const Plan& pl, ctws_block* b
     add_timing(h, "auto_seeded_blocks", (float)n_auto_blocks);
     add_timing(h, "sf_sparse_blocks", (float)n_sf_sparse);
     add_timing(h, "sf_redo_blocks", (float)n_sf_redo);
+    add_timing(h, "hist_fused", counts_ready ? 1.f : 0.f);  // batches whose flood check counted the labels
     add_timing(h, "flood_kernel_ms", fk1);
     add_timing(h, "flood_packed", packed ? 1.f : 0.f);
     add_timing(h, "flood_tiles_solved", (float)h->flood_tiles);
@@ -2509,6 +2535,7 @@ int ctws_open(int device, ctws_handle** out) {
     if (const char* t = std::getenv("CTWS_NO_FALLBACK")) h->no_fallback = std::atoi(t);
     if (const char* t = std::getenv("CTWS_FORCE_WIDE")) h->force_wide = std::atoi(t);
     if (const char* t = std::getenv("CTWS_SF_SPARSE")) h->sf_sparse = std::atoi(t);
+    if (const char* t = std::getenv("CTWS_FUSE_HIST")) h->fuse_hist = std::atoi(t);
     if (const char* t = std::getenv("CTWS_VERIFY")) h->verify = std::atoi(t);
     if (const char* t = std::getenv("CTWS_PREP_LDS")) h->prep_lds = std::atoi(t);
     if (const char* t = std::getenv("CTWS_EDT_BITS")) h->edt_bits = std::atoi(t);
@@ -2572,7 +2599,7 @@ void ctws_close(ctws_handle* h) {
     void* ptrs[] = {w.fin, w.dt, w.A, w.Bf, w.sm, w.hm, w.cls, w.P, w.PF, w.lab, w.key, w.W, w.Wp, w.csum,
                     w.smin, w.smax, w.sb, w.slmax, w.soff, w.surv, w.act0, w.act1, w.lines0, w.lines1, w.desc, w.stat, w.counter,
                     w.taps, w.hkey, w.hpos, w.p2err, w.front0, w.front1, w.fopen, w.fflags, w.fchunk0, w.fchunk1, w.wl0, w.wl1, w.qgen, w.wlcnt,
-                    w.fstat, h->st_in.p, h->st_mask.p, h->st_init.p, h->st_out.p, h->rl_lab.p, h->rl_bits.p,
+                    w.fstat, w.sfacc, h->st_in.p, h->st_mask.p, h->st_init.p, h->st_out.p, h->rl_lab.p, h->rl_bits.p,
                     h->rl_cnt.p, h->rl_offs.p, h->rl_out.p, h->rl_keys.p, h->rl_vals.p, h->rl_red.p,
                     h->edt_fh.p, h->edt_scratch.p, h->p2_hint_dev.p, h->rl_sorted.p, h->rl_uniq.p, h->rl_counts.p, h->rl_tmp.p,
                     h->fs_vals.p, h->fs_sorted.p, h->fs_off.p, h->fs_tmp.p, h->sf_ids.p, h->sf_bits.p, h->sf_desc.p,

@@ -422,6 +422,20 @@ __device__ __forceinline__ uint64_t shfl_down_u64(uint64_t v, int d) {
     return (uint64_t)__shfl_down((long long)v, d);
 }
 
+// count a wave's labels: one add per run of equal labels in consecutive lanes (voxels along x
+// mostly share their label, so a mixed wave is a few runs, not 64 atomics on the same bins).
+// ok: the lane holds a label to count (the invalid lanes are a tail of the wave)
+template <class Add>
+__device__ __forceinline__ void count_label_runs(uint32_t l, bool ok, int lane, Add add) {
+    const uint32_t prev = (uint32_t)__shfl_up((int)l, 1);
+    const uint64_t act = __ballot(ok);
+    const uint64_t starts = __ballot(ok && (lane == 0 || prev != l));
+    if (!((starts >> lane) & 1ull)) return;
+    const uint64_t ends = (starts | ~act) & ~((2ull << lane) - 1ull);  // run boundaries above the lane
+    const int next = ends ? __builtin_ctzll(ends) : 64;
+    add(l, (uint32_t)(next - lane));
+}
+
 // ---- packed flood keys: C (ordered float bits, 32) | d (12, saturating) | label (20) ----------
 constexpr uint64_t kPackInf = ~0ull;
 constexpr uint32_t kLabelBits = 20;

@@ -239,6 +239,10 @@ __global__ void k_frontier_tiles(const BlockDesc*, const BlockStat*, const uint6
 template <int ND>
 __global__ void k_flood_verify(const BlockDesc*, const BlockStat*, const float*, const uint64_t*, const uint64_t*,
                                uint32_t*);
+constexpr int kHist2dBins = 8192;  // LDS bins of the per-slice histograms (k_hist2d, k_flood_verify_hist2d)
+constexpr int kVerifyHistThreads = 256;  // workgroup of k_flood_verify_hist2d
+__global__ void k_flood_verify_hist2d(const BlockDesc*, const BlockStat*, const float*, const uint64_t*,
+                                      const uint64_t*, const uint32_t*, uint32_t*, uint32_t*, int, int);
 constexpr int kWordWaves = 4;  // waves per workgroup of the word-tiled kernels
 __global__ void k_flood_reset(const BlockDesc*, const BlockStat*, const float*, const uint32_t*, const uint32_t*,
                               const uint64_t*, uint64_t*, uint8_t*);
@@ -256,8 +260,10 @@ __global__ void k_slice_max(const BlockDesc*, const BlockStat*, const uint32_t*,
 template <int PACKED>
 __global__ void k_hist2d(const BlockDesc*, const BlockStat*, const uint32_t*, const uint64_t*, const uint32_t*,
                          uint32_t*, int);
+constexpr int kSfPlanSplit = 32;      // workgroups per block of k_sf_plan, at the most
+constexpr int kSfPlanLabels = 4096;   // labels per workgroup of k_sf_plan
 __global__ void k_sf_plan(const BlockDesc*, BlockStat*, uint32_t, const uint32_t*, const uint8_t*, const uint32_t*,
-                          uint32_t*);
+                          uint32_t*, uint32_t*);
 __global__ void k_sf_sparse(const BlockDesc*, BlockStat*, uint32_t, const uint32_t*, const uint8_t*,
                             const uint32_t*, const float*, uint64_t*, uint8_t*, uint64_t*, uint64_t*);
 __global__ void k_fixed_from_open(const BlockDesc*, const BlockStat*, const uint64_t*, uint8_t*);

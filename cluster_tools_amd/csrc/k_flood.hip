@@ -1408,6 +1408,141 @@ template __global__ void k_flood_verify<3>(const BlockDesc*, const BlockStat*, c
 template __global__ void k_flood_verify<2>(const BlockDesc*, const BlockStat*, const float*, const uint64_t*,
                                            const uint64_t*, uint32_t*);
 
+// The first flood's check in 2-D ws mode, which also counts the labels for the size filter (the
+// check of k_flood_verify<2> and the histogram of k_hist2d over one read of the keys: after the
+// first flood nearly every unit holds an open voxel, so the check reads every key anyway).
+// Laid out as k_hist2d: a workgroup takes a quarter (1 / splits) of one slice's units and counts
+// into an LDS histogram of the slice's label range (sb[z], sb[z + 1]], global atomics above
+// `bins` labels.  The host sizes the dynamic LDS to the batch's labels per slice (bins <=
+// kHist2dBins): with three batches in flight on three streams a 256-thread workgroup with a few
+// KiB of LDS finds room next to the other streams' kernels, which one with 32 KiB does not.
+// Every unit's centre rows are counted; a unit without an open voxel skips the height and x-edge
+// loads and the check, as in k_flood_verify.  The units of the quarter are split evenly over the
+// workgroup's waves, strip-major (vertically adjacent units share rows).
+__global__ void __launch_bounds__(kVerifyHistThreads) __attribute__((amdgpu_waves_per_eu(6, 8)))
+k_flood_verify_hist2d(const BlockDesc* __restrict__ D, const BlockStat* S, const float* __restrict__ h,
+                      const uint64_t* __restrict__ key, const uint64_t* __restrict__ open,
+                      const uint32_t* __restrict__ sb, uint32_t* __restrict__ counts, uint32_t* __restrict__ flag,
+                      int splits, int bins) {
+    extern __shared__ uint32_t sh[];
+    const BlockDesc& B = D[blockIdx.y];
+    if (!S[blockIdx.y].active) return;
+    const int z = blockIdx.x / splits, s = blockIdx.x % splits;
+    if (z >= B.Z) return;
+    const uint32_t b0 = sb[B.sbase + z];
+    const uint32_t b1 = z + 1 < B.Z ? sb[B.sbase + z + 1] : S[blockIdx.y].n_seeds;
+    const uint32_t nb = b1 - b0;  // labels b0 + 1 .. b1 -> bins 0 .. nb - 1
+    const bool use_lds = nb <= (uint32_t)bins;
+    if (use_lds)
+        for (uint32_t j = threadIdx.x; j < nb; j += blockDim.x) sh[j] = 0;
+    __syncthreads();
+    uint32_t* c = counts + B.base + b0 + 1;
+    constexpr int U = 4, R = U + 2;
+    // the slice's keys, heights and open words (in-slice offsets fit 32 bits)
+    const int64_t zb = (int64_t)z * B.Y * B.X;
+    const int wpr = (B.X + 63) >> 6;
+    const gptr_t<uint64_t> k = gbl(key + B.base + zb);
+    const gptr_t<float> hb = gbl(h + B.base + zb);
+    const gptr_t<uint64_t> ob = gbl(open + B.fbase + (int64_t)z * B.Y * wpr);
+    const int ngy = (B.Y + U - 1) / U;
+    const int nu = wpr * ngy;  // units of the slice
+    const int q0 = (int)((int64_t)nu * s / splits), q1 = (int)((int64_t)nu * (s + 1) / splits);
+    const int lane = threadIdx.x & 63;
+    const int nw = (int)(blockDim.x >> 6);
+    const int per = (q1 - q0 + nw - 1) / nw;
+    const int ubeg = q0 + (int)(threadIdx.x >> 6) * per, uend = min(q1, ubeg + per);
+    bool bad = false, dsat = false;
+    // 64 units at a time: lane l loads the open words of unit un0 + l
+    for (int un0 = ubeg; un0 < uend; un0 += 64) {
+        uint64_t lw[U];
+        {
+            const int ul = un0 + lane;
+            const int xwl = ul / ngy, gyl = ul - xwl * ngy;
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                lw[u] = (ul < uend && gyl * U + u < B.Y)
+                            ? ob[(gyl * U + u) * wpr + xwl]
+                            : 0ull;
+        }
+        const uint64_t has_open = __ballot((lw[0] | lw[1] | lw[2] | lw[3]) != 0ull);
+        const int cnt = min(64, uend - un0);
+        for (int src = 0; src < cnt; ++src) {
+            const int un = un0 + src;
+            const int xw = un / ngy, gy = un - xw * ngy;
+            const int y0 = gy * U;
+            const bool any_open = (has_open >> src) & 1ull;  // (wave-uniform)
+            const int x = xw * 64 + lane;
+            const int xc = min(x, B.X - 1);
+            const int xe = lane == 0 ? max(xc - 1, 0) : min(xc + 1, B.X - 1);
+            uint64_t rk[R];
+#pragma unroll
+            for (int q = 0; q < R; ++q) {
+                const int yy = min(max(y0 - 1 + q, 0), B.Y - 1);
+                rk[q] = k[yy * B.X + xc];
+            }
+            uint64_t ke[U];
+            float hv[U];
+            if (any_open) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const int yy = min(y0 + u, B.Y - 1);
+                    ke[u] = k[yy * B.X + xe];
+                    hv[u] = hb[yy * B.X + xc];
+                }
+            } else {
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    ke[u] = kPackInf;
+                    hv[u] = 0.f;
+                }
+            }
+            // the centre rows' labels (0, unreached, is not counted: k_sf_plan derives it)
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const uint64_t kv = rk[u + 1];
+                const uint32_t l = kv == kPackInf ? 0u : (uint32_t)(kv & kLabelMask);
+                // (a row below the block: no lane counts)
+                count_label_runs(l, y0 + u < B.Y && x < B.X, lane, [&](uint32_t lb, uint32_t n) {
+                    if (lb <= b0 || lb > b1) return;
+                    if (use_lds) atomicAdd(&sh[lb - b0 - 1], n);
+                    else atomicAdd(&c[lb - b0 - 1], n);
+                });
+            }
+            if (!any_open) continue;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int y = y0 + u;
+                const bool valid = y < B.Y && x < B.X;
+                const uint64_t o = valid ? rk[u + 1] : kPackInf;
+                uint64_t l = shfl_up_u64(o, 1), r = shfl_down_u64(o, 1);
+                const uint64_t ker = shfl_u64(ke[u], 63);
+                if (lane == 0) l = (x > 0) ? ke[u] : kPackInf;
+                if (lane == 63) r = ker;
+                if (x + 1 >= B.X) r = kPackInf;
+                uint64_t m = min(l, r);
+                if (y > 0) m = min(m, rk[u]);
+                if (y + 1 < B.Y) m = min(m, rk[u + 2]);
+                // (an open voxel is never a seed: k_flood_verify)
+                const uint64_t e = (m == kPackInf) ? kPackInf : f_packed(ordf(hv[u]), m);
+                const bool isopen = valid && ((shfl_u64(lw[u], src) >> lane) & 1ull);
+                const bool b1v = isopen && e != o;
+                dsat |= isopen && key_dsat(o);
+                if (b1v && flag[1] < 8u) {  // diagnostics: the first few violations
+                    const uint32_t slot = atomicAdd(&flag[1], 1u);
+                    if (slot < 8u) flag[2 + slot] = (uint32_t)(B.base + (int64_t)z * B.Y * B.X + y * B.X + x);
+                }
+                bad |= b1v;
+            }
+        }
+    }
+    if (__ballot(bad) && lane == 0) atomicOr(flag, 1u);
+    if (__ballot(dsat) && lane == 0) note_dsat(S, blockIdx.y);
+    if (!use_lds) return;
+    __syncthreads();
+    for (uint32_t j = threadIdx.x; j < nb; j += blockDim.x)
+        if (sh[j]) atomicAdd(&c[j], sh[j]);
+}
+
 // seeds only (fallback after a failed verification)
 __global__ void __launch_bounds__(256) k_flood_reset(const BlockDesc* __restrict__ D, const BlockStat* S,
                                                      const float* __restrict__ h, const uint32_t* __restrict__ lab,

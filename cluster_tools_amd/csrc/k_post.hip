@@ -38,20 +38,6 @@ __global__ void __launch_bounds__(256) k_hist_zero(const BlockDesc* __restrict__
         counts[B.base + i] = 0;
 }
 
-// count a wave's labels: one add per run of equal labels in consecutive lanes (voxels along x
-// mostly share their label, so a mixed wave is a few runs, not 64 atomics on the same bins).
-// ok: the lane holds a label to count (the invalid lanes are a tail of the wave)
-template <class Add>
-__device__ __forceinline__ void count_label_runs(uint32_t l, bool ok, int lane, Add add) {
-    const uint32_t prev = (uint32_t)__shfl_up((int)l, 1);
-    const uint64_t act = __ballot(ok);
-    const uint64_t starts = __ballot(ok && (lane == 0 || prev != l));
-    if (!((starts >> lane) & 1ull)) return;
-    const uint64_t ends = (starts | ~act) & ~((2ull << lane) - 1ull);  // run boundaries above the lane
-    const int next = ends ? __builtin_ctzll(ends) : 64;
-    add(l, (uint32_t)(next - lane));
-}
-
 // label counts over the whole outer block (3-D) / slice (2-D: labels are slice-unique).
 // Each workgroup counts a contiguous range in an LDS histogram of `bins` entries (dynamic
 // LDS, sized by the host to the batch's largest seed count so that a few thousand labels do
@@ -110,7 +96,8 @@ __global__ void __launch_bounds__(256) k_hist(const BlockDesc* __restrict__ D, c
 // 2-D ws: the labels of slice z are the block labels (sb[z], sb[z + 1]] (seeds are numbered
 // slice-major), so each workgroup counts a quarter of one slice into a small LDS histogram of
 // that range — no contention on a block-wide table of tens of thousands of labels.
-constexpr int kHist2dBins = 8192;
+// (After the first flood of a packed pass-1 batch the fixpoint check counts instead:
+// k_flood_verify_hist2d, k_flood.hip.)
 template <int PACKED>
 __global__ void __launch_bounds__(256) k_hist2d(const BlockDesc* __restrict__ D, const BlockStat* S,
                                                 const uint32_t* __restrict__ lab, const uint64_t* __restrict__ key,
@@ -187,17 +174,26 @@ __device__ __forceinline__ bool sf_keeps(const uint32_t* c, const uint8_t* ex, u
     return c[l] >= size_filter || (ex && ex[l]);
 }
 
+// The plan of one block is taken by gridDim.x workgroups (one would walk a block's ~10^5 labels
+// serially on an otherwise empty chip; the host takes one per kSfPlanLabels labels of the batch's
+// largest block, kSfPlanSplit at the most): each sums its range of the labels and tests its share
+// of the slices (a wave per slice), the sums meet in acc[4 * block] (nsmall, tot, bare, arrivals:
+// zero between launches), and the workgroup that arrives last decides and zeroes them again.
 __global__ void __launch_bounds__(256) k_sf_plan(const BlockDesc* __restrict__ D, BlockStat* S, uint32_t size_filter,
                                                  const uint32_t* __restrict__ counts, const uint8_t* __restrict__ excl,
-                                                 const uint32_t* __restrict__ sb, uint32_t* __restrict__ survivors) {
-    const BlockDesc& B = D[blockIdx.x];
-    BlockStat& st = S[blockIdx.x];
+                                                 const uint32_t* __restrict__ sb, uint32_t* __restrict__ survivors,
+                                                 uint32_t* __restrict__ acc) {
+    const BlockDesc& B = D[blockIdx.y];
+    BlockStat& st = S[blockIdx.y];
     if (!st.active) return;
     const uint32_t ns = st.n_seeds;
     const uint32_t* c = counts + B.base;
     const uint8_t* ex = excl ? excl + B.base : nullptr;
+    uint32_t* a = acc + 4 * blockIdx.y;
+    const uint32_t per = (ns + gridDim.x - 1) / gridDim.x;
+    const uint32_t la = 1u + blockIdx.x * per, lb = min(ns, la + per - 1u);
     uint32_t nsmall = 0, tot = 0;
-    for (uint32_t l = 1 + threadIdx.x; l <= ns; l += 256) {
+    for (uint32_t l = la + threadIdx.x; l <= lb; l += 256) {
         nsmall += sf_keeps(c, ex, l, size_filter) ? 0u : 1u;
         tot += c[l];
     }
@@ -205,19 +201,40 @@ __global__ void __launch_bounds__(256) k_sf_plan(const BlockDesc* __restrict__ D
     // the voxels without a label (unreached by the flood): the block's voxels the labels' counts
     // leave over (every labelled voxel is counted once, 2-D slices in their own label ranges)
     tot = wg_reduce_u32(tot, OpAdd());
-    // every slice (2-D) / the block (3-D) keeps a segment: no auto-seeded regrow
+    // every slice (2-D) / the block (3-D: below) keeps a segment: no auto-seeded regrow
     uint32_t bare = 0;
     if (B.nd_ws == 2) {
-        for (int z = threadIdx.x; z < B.Z; z += 256) {
+        const int lane = threadIdx.x & 63;
+        for (int z = blockIdx.x * 4 + (threadIdx.x >> 6); z < B.Z; z += gridDim.x * 4) {
             const uint32_t l0 = sb[B.sbase + z], l1 = z + 1 < B.Z ? sb[B.sbase + z + 1] : ns;
             bool any = false;
-            for (uint32_t l = l0 + 1; l <= l1 && !any; ++l) any = sf_keeps(c, ex, l, size_filter);
-            bare += any ? 0u : 1u;
+            for (uint32_t l = l0 + 1; l <= l1 && !any; l += 64)
+                any = __ballot(l + lane <= l1 && sf_keeps(c, ex, l + lane, size_filter)) != 0ull;
+            bare += (lane == 0 && !any) ? 1u : 0u;
         }
-    } else {
-        bare = threadIdx.x == 0 && nsmall == ns ? 1u : 0u;
     }
     bare = wg_reduce_u32(bare, OpAdd());
+    // thread 0 adds the workgroup's sums and, in the workgroup that arrives last, reads the
+    // block's totals and zeroes the words (every workgroup has arrived); the other threads get the
+    // totals through LDS behind the barrier, never from the words that are being zeroed
+    __shared__ uint32_t last, totals[3];
+    if (threadIdx.x == 0) {
+        atomicAdd(&a[0], nsmall);
+        atomicAdd(&a[1], tot);
+        atomicAdd(&a[2], bare);
+        __threadfence();
+        last = atomicAdd(&a[3], 1u) == gridDim.x - 1 ? 1u : 0u;
+        if (last) {
+            __threadfence();
+            for (int j = 0; j < 3; ++j) totals[j] = atomicAdd(&a[j], 0u);
+            for (int j = 0; j < 4; ++j) a[j] = 0u;
+        }
+    }
+    __syncthreads();
+    if (!last) return;
+    nsmall = totals[0];
+    tot = totals[1];
+    bare = B.nd_ws == 2 ? totals[2] : (nsmall == ns ? 1u : 0u);
     const uint32_t unreached = (uint32_t)B.N - tot;
     const bool sparse = size_filter <= kSfSparseMax && !unreached && !bare &&
                         (uint64_t)nsmall * size_filter <= (uint64_t)B.N / 8;
