@@ -3250,17 +3250,173 @@ int ctws_lookup_u64(ctws_handle* h, uint64_t* labels, int64_t n, int on_device, 
     return CTWS_OK;
 }
 
-// ---- GraphWorkflow: the region adjacency graph (k_rag.hip) ----------------------------------
+// ---- the scaffold of the feature block calls below -------------------------------------------
 extern "C++" {
 namespace {
-constexpr size_t kRagRed = 32;  // counter words of rg_red
+// The words of a feature's counter block (rg_red; the edge features' own ef_red).  The appends of
+// all waves meet in an append counter, so each of the two has a 128-B line (16 words) to itself.
+enum RedWord : size_t {
+    kRedEmit = 0,       // the append counter of a counted emit
+    kRedPairRuns = 1,   // pairs_tail: the unique pairs ...
+    kRedPairMiss = 2,   // ... and the endpoint values missing from the id table
+    kRedNodes = 16,     // graph: the append counter of the node ids
+    kRedVmax = 16,      // morphology, region features: the largest id
+    kRedMissing = 16,   // edge features: the owned voxel pairs without an edge
+    kRedBadEdges = 17,  // edge features: edges not sorted, not unique or off the nodes
+    kRedRuns = 19,      // sort_by_id: the distinct ids
+    kRedWords = 32
+};
 
 // the stage between events a and b of this call, in ms
-void rag_time(ctws_handle* h, const char* name, size_t a, size_t b) {
+void stage_time(ctws_handle* h, const char* name, size_t a, size_t b) {
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, h->events[a], h->events[b]) == hipSuccess) add_timing(h, name, ms);
 }
 
+int call_begin(ctws_handle* h) {
+    h->err.clear();
+    h->timings.clear();
+    HIPCHK(hipSetDevice(h->device));
+    return CTWS_OK;
+}
+
+// the kernels index a block with 32 bits: every extent and product of extents stays below 2^31
+int check_extent(ctws_handle* h, int64_t nz, int64_t ny, int64_t nx, const char* what, const char* unit,
+                 const char* why) {
+    constexpr int64_t kMax = 1ll << 31;
+    if (nz >= kMax || ny >= kMax || nx >= kMax || nz * ny >= kMax || nz * ny * nx >= kMax) {
+        h->err = std::string(what) + ": 2^31 or more voxels in one " + unit + " (" + why + ")";
+        return CTWS_EUNSUPPORTED;
+    }
+    return CTWS_OK;
+}
+
+// An input array of a call -> *d, the device pointer to read: the caller's own with dev, else its
+// copy in b.
+template <class T>
+int stage_in(ctws_handle* h, DevBuf& b, const T* src, size_t bytes, bool dev, const T** d) {
+    *d = src;
+    if (dev) return CTWS_OK;
+    const int r = grow(h, b, bytes);
+    if (r != CTWS_OK) return r;
+    HIPCHK(copy_pieces(b.p, src, bytes, hipMemcpyHostToDevice, h->stream));
+    *d = (const T*)b.p;
+    return CTWS_OK;
+}
+
+// A result array of a call.  out_begin -> *d, the device pointer to write: the caller's own with
+// dev, else b.  out_end ends the call: the download for a host caller, and the one wait.
+template <class T>
+int out_begin(ctws_handle* h, DevBuf& b, T* dst, size_t bytes, bool dev, T** d) {
+    *d = dst;
+    if (dev) return CTWS_OK;
+    const int r = grow(h, b, bytes);
+    *d = (T*)b.p;
+    return r;
+}
+
+int out_end(ctws_handle* h, void* dst, const void* d, size_t bytes, bool dev) {
+    if (!dev) HIPCHK(copy_pieces(dst, d, bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return CTWS_OK;
+}
+
+// The counted emit.  A kernel appends records to buffers and counts every append, also those that
+// found no room.  First capacities that depend on the block alone (so a call behaves the same
+// whatever the handle ran before); the pass is repeated once at the counted sizes when one did
+// not fit.
+struct EmitCap {
+    RedWord word;            // the counter that ...
+    unsigned long long cap;  // ... this capacity bounds
+};
+struct Emitted {
+    unsigned long long w[kRedWords] = {0};  // the counters as read back
+    int passes = 0;
+};
+unsigned long long first_cap(int64_t n, int64_t div) { return (unsigned long long)std::max<int64_t>(64, n / div); }
+
+// cnt: the counter block; its first nzero words are zeroed before a pass and nread read back after
+// it.  launch() grows the record buffers to caps and launches; check(w) is the feature's own look
+// at the counters of a pass.
+template <class Launch, class Check>
+int counted_emit(ctws_handle* h, const char* what, unsigned long long* cnt, size_t nzero, size_t nread, EmitCap* caps,
+                 int ncaps, Launch launch, Check check, Emitted* e) {
+    int r, attempt = 0;
+    for (; attempt < 2; ++attempt) {
+        HIPCHK(hipMemsetAsync(cnt, 0, nzero * sizeof(uint64_t), h->stream));
+        if ((r = launch()) != CTWS_OK) return r;
+        LAUNCHCHK();
+        HIPCHK(hipMemcpyAsync(e->w, cnt, nread * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if ((r = check(e->w)) != CTWS_OK) return r;
+        bool fit = true;
+        for (int c = 0; c < ncaps; ++c) fit = fit && e->w[caps[c].word] <= caps[c].cap;
+        if (fit) break;
+        if (attempt == 1) {
+            h->err = std::string(what) + ": the emit counts changed between two passes over the same input";
+            return CTWS_EHIP;
+        }
+        for (int c = 0; c < ncaps; ++c) caps[c].cap = std::max(caps[c].cap, e->w[caps[c].word]);
+    }
+    e->passes = attempt + 1;
+    return CTWS_OK;
+}
+
+// a check of counted_emit: at least lo runs and at most one per voxel, or no second pass helps
+int runs_within(ctws_handle* h, const char* what, unsigned long long runs, int64_t lo, int64_t n) {
+    if (runs >= (unsigned long long)lo && runs <= (unsigned long long)n) return CTWS_OK;
+    h->err = std::string(what) + ": the kernel counted " + std::to_string(runs) + " runs in " + std::to_string(n) +
+             " voxels";
+    return CTWS_EHIP;
+}
+
+// Sort by id and run-length encode: n (id, record) pairs on the device -> the pairs sorted by id
+// (rg_skeys, rg_sw) and the distinct ids with their numbers of pairs (rg_keys, rg_sum).  vmax: the
+// largest id, for the sort's bits; the ids become float64 columns, so 2^53 or more is refused.
+// ev: the event recorded behind the two launches.  The counters are those of rg_red.
+struct ById {
+    uint64_t *sids, *srecs, *uniq, *counts;
+    int64_t m;  // the distinct ids
+};
+int sort_by_id(ctws_handle* h, const char* what, const uint64_t* ids, const uint64_t* recs, int64_t n,
+               unsigned long long vmax, size_t ev, ById* o) {
+    if (vmax >= (1ull << 53)) {
+        h->err = std::string(what) + ": an id of 2^53 or more (" + std::to_string(vmax) +
+                 ") has no exact place in the float64 rows";
+        return CTWS_EUNSUPPORTED;
+    }
+    int bits = 1;
+    while (bits < 53 && (1ull << bits) <= vmax) ++bits;
+    int r;
+    const size_t nb = sizeof(uint64_t) * (size_t)n;
+    size_t tb_sort = 0, tb_rle = 0;
+    HIPCHK(pair_sort(nullptr, tb_sort, nullptr, nullptr, nullptr, nullptr, n, bits, h->stream));
+    HIPCHK(u64_runs(nullptr, tb_rle, nullptr, nullptr, nullptr, nullptr, n, h->stream));
+    if ((r = grow(h, h->rg_skeys, nb)) != CTWS_OK) return r;
+    if ((r = grow(h, h->rg_sw, nb)) != CTWS_OK) return r;
+    if ((r = grow(h, h->rg_keys, nb)) != CTWS_OK) return r;
+    if ((r = grow(h, h->rg_sum, nb)) != CTWS_OK) return r;
+    if ((r = grow(h, h->rg_tmp, std::max(tb_sort, tb_rle))) != CTWS_OK) return r;
+    o->sids = (uint64_t*)h->rg_skeys.p;
+    o->srecs = (uint64_t*)h->rg_sw.p;
+    o->uniq = (uint64_t*)h->rg_keys.p;
+    o->counts = (uint64_t*)h->rg_sum.p;
+    uint64_t* nruns = (uint64_t*)h->rg_red.p + kRedRuns;
+    HIPCHK(pair_sort(h->rg_tmp.p, tb_sort, ids, o->sids, recs, o->srecs, n, bits, h->stream));
+    HIPCHK(u64_runs(h->rg_tmp.p, tb_rle, o->sids, o->uniq, o->counts, nruns, n, h->stream));
+    record(h, ev);
+    unsigned long long runs = 0;
+    HIPCHK(hipMemcpyAsync(&runs, nruns, sizeof(runs), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (runs == 0 || runs > (unsigned long long)n) {
+        h->err = std::string(what) + ": " + std::to_string(runs) + " ids from " + std::to_string(n) + " runs";
+        return CTWS_EHIP;
+    }
+    o->m = (int64_t)runs;
+    return CTWS_OK;
+}
+
+// ---- GraphWorkflow: the region adjacency graph (k_rag.hip) ----------------------------------
 // The sorted distinct values of dv (device) into rg_tab, by the relabel path's radix sort and
 // run-length encoding: these are id tables with many repeats of few values over a narrow range,
 // where the bitmap unique's atomics all land in a few words (57 ms for the 16.8 M labels of a
@@ -3308,30 +3464,31 @@ int pairs_tail(ctws_handle* h, const uint64_t* pairs, const uint64_t* weights, i
     if ((r = grow(h, h->rg_sw, nb)) != CTWS_OK) return r;
     if ((r = grow(h, h->rg_sum, nb)) != CTWS_OK) return r;
     if ((r = grow(h, h->rg_tmp, std::max(tb_sort, tb_red))) != CTWS_OK) return r;
-    if ((r = grow(h, h->rg_red, kRagRed * sizeof(uint64_t))) != CTWS_OK) return r;
+    if ((r = grow(h, h->rg_red, kRedWords * sizeof(uint64_t))) != CTWS_OK) return r;
     if (!weights && (r = grow(h, h->rg_w, nb)) != CTWS_OK) return r;
     uint64_t* keys = (uint64_t*)h->rg_keys.p;
     uint64_t* skeys = (uint64_t*)h->rg_skeys.p;
     uint64_t* sw = (uint64_t*)h->rg_sw.p;
     uint64_t* sums = (uint64_t*)h->rg_sum.p;
-    unsigned long long* red = (unsigned long long*)h->rg_red.p;  // [1] runs, [2] missing
+    unsigned long long* red = (unsigned long long*)h->rg_red.p;
     const unsigned g = (unsigned)std::min<int64_t>((n + 255) / 256, 8192);
-    HIPCHK(hipMemsetAsync(red + 1, 0, 2 * sizeof(uint64_t), h->stream));
+    HIPCHK(hipMemsetAsync(red + kRedPairRuns, 0, 2 * sizeof(uint64_t), h->stream));  // (and kRedPairMiss)
     record(h, 2);
     if (!weights) {
         k_pair_ones<<<g, 256, 0, h->stream>>>((uint64_t*)h->rg_w.p, n);
         weights = (const uint64_t*)h->rg_w.p;
     }
-    k_pair_keys<<<g, 256, 0, h->stream>>>(pairs, n, tab, nt, b, keys, red + 2);
+    k_pair_keys<<<g, 256, 0, h->stream>>>(pairs, n, tab, nt, b, keys, red + kRedPairMiss);
     LAUNCHCHK();
     record(h, 3);
     HIPCHK(pair_sort(h->rg_tmp.p, tb_sort, keys, skeys, weights, sw, n, 2 * b, h->stream));
     record(h, 4);
     // (the unsorted keys are dead: their buffer takes the unique keys)
-    HIPCHK(pair_reduce(h->rg_tmp.p, tb_red, skeys, keys, sw, sums, (uint64_t*)(red + 1), n, h->stream));
+    HIPCHK(pair_reduce(h->rg_tmp.p, tb_red, skeys, keys, sw, sums, (uint64_t*)(red + kRedPairRuns), n,
+                       h->stream));
     record(h, 5);
     unsigned long long hr[2] = {0ull, 0ull};
-    HIPCHK(hipMemcpyAsync(hr, red + 1, sizeof(hr), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(hr, red + kRedPairRuns, sizeof(hr), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     if (hr[1]) {
         h->err = "unique pairs: " + std::to_string(hr[1]) + " endpoint values are missing from the id table";
@@ -3344,10 +3501,10 @@ int pairs_tail(ctws_handle* h, const uint64_t* pairs, const uint64_t* weights, i
     LAUNCHCHK();
     record(h, 6);
     HIPCHK(hipStreamSynchronize(h->stream));
-    rag_time(h, "pair_keys", 2, 3);
-    rag_time(h, "pair_sort", 3, 4);
-    rag_time(h, "pair_reduce", 4, 5);
-    rag_time(h, "pair_unpack", 5, 6);
+    stage_time(h, "pair_keys", 2, 3);
+    stage_time(h, "pair_sort", 3, 4);
+    stage_time(h, "pair_reduce", 4, 5);
+    stage_time(h, "pair_unpack", 5, 6);
     return CTWS_OK;
 }
 
@@ -3368,28 +3525,17 @@ int rag_block(ctws_handle* h, const uint64_t* labels, int64_t nz, int64_t ny, in
     if (!h || !labels || nz <= 0 || ny <= 0 || nx <= 0 || !n_nodes || !n_edges || cap_nodes < 0 || cap_edges < 0 ||
         (!nodes && cap_nodes > 0) || (!edges && cap_edges > 0))
         return CTWS_EINVAL;
-    h->err.clear();
-    h->timings.clear();
-    HIPCHK(hipSetDevice(h->device));
-    *n_nodes = *n_edges = 0;
-    constexpr int64_t kMax = 1ll << 31;
-    if (nz >= kMax || ny >= kMax || nx >= kMax || nz * ny >= kMax || nz * ny * nx >= kMax) {
-        h->err = "rag block: 2^31 or more voxels in one block (the pair kernel indexes a block with 32 bits)";
-        return CTWS_EUNSUPPORTED;
-    }
-    const int64_t N = nz * ny * nx;
     int r;
-    const uint64_t* dl = labels;
-    if (!dev) {
-        if ((r = grow(h, h->rg_lab, sizeof(uint64_t) * (size_t)N)) != CTWS_OK) return r;
-        HIPCHK(copy_pieces(h->rg_lab.p, labels, sizeof(uint64_t) * (size_t)N, hipMemcpyHostToDevice, h->stream));
-        dl = (const uint64_t*)h->rg_lab.p;
-    }
-    // one pass emits the pairs and the node ids.  First buffers of a quarter / a sixteenth of the
-    // voxels (the sizes depend on the block alone, so a call behaves the same whatever the handle
-    // ran before); the emission is repeated with the counted sizes when one did not fit
-    if ((r = grow(h, h->rg_red, kRagRed * sizeof(uint64_t))) != CTWS_OK) return r;
-    // [0] pairs, [16] nodes: a 128-B line each (the appends of all waves meet in these two words)
+    if ((r = call_begin(h)) != CTWS_OK) return r;
+    *n_nodes = *n_edges = 0;
+    r = check_extent(h, nz, ny, nx, "rag block", "block", "the pair kernel indexes a block with 32 bits");
+    if (r != CTWS_OK) return r;
+    const int64_t N = nz * ny * nx;
+    const uint64_t* dl;
+    if ((r = stage_in(h, h->rg_lab, labels, sizeof(uint64_t) * (size_t)N, dev, &dl)) != CTWS_OK) return r;
+    // one pass emits the pairs and the node ids, into first buffers of a quarter / a sixteenth of
+    // the voxels
+    if ((r = grow(h, h->rg_red, kRedWords * sizeof(uint64_t))) != CTWS_OK) return r;
     unsigned long long* cnt = (unsigned long long*)h->rg_red.p;
     RagArgs a;
     a.lab = dl;
@@ -3398,54 +3544,48 @@ int rag_block(ctws_handle* h, const uint64_t* labels, int64_t nz, int64_t ny, in
     a.nx = (uint32_t)nx;
     a.ignore = ignore_label ? 1 : 0;
     a.count = cnt;
-    a.ncount = cnt + 16;
+    a.ncount = cnt + kRedNodes;
     const int64_t rows = nz * ny;
     // four workgroups per CU (their LDS stages) and no more: every wave ends with an append of
     // its own, and one counter word takes only ~85 returning atomics per microsecond
     const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>((rows + 3) / 4, 1024));
-    unsigned long long emitted[17] = {0};
-    unsigned long long cap = (unsigned long long)std::max<int64_t>(64, N / 4);
-    unsigned long long ncap = (unsigned long long)std::max<int64_t>(64, N / 16);
+    EmitCap caps[2] = {{kRedEmit, first_cap(N, 4)}, {kRedNodes, first_cap(N, 16)}};
+    Emitted e;
     record(h, 0);
-    int attempt = 0;
-    for (; attempt < 2; ++attempt) {
-        if ((r = grow(h, h->rg_pairs, 2 * sizeof(uint64_t) * (size_t)cap)) != CTWS_OK) return r;
-        if ((r = grow(h, h->rg_w, sizeof(uint64_t) * (size_t)cap)) != CTWS_OK) return r;
-        if ((r = grow(h, h->rg_nodes, sizeof(uint64_t) * (size_t)ncap)) != CTWS_OK) return r;
-        a.pairs = (uint64_t*)h->rg_pairs.p;
-        a.weights = (uint64_t*)h->rg_w.p;
-        a.nodes = (uint64_t*)h->rg_nodes.p;
-        a.cap = cap;
-        a.ncap = ncap;
-        HIPCHK(hipMemsetAsync(cnt, 0, 17 * sizeof(uint64_t), h->stream));
-        k_rag_pairs<<<g, 256, 0, h->stream>>>(a);
-        LAUNCHCHK();
-        HIPCHK(hipMemcpyAsync(emitted, cnt, sizeof(emitted), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if (emitted[0] <= cap && emitted[16] <= ncap) break;
-        if (attempt == 1) {
-            h->err = "rag block: the emit counts changed between two passes over the same labels";
-            return CTWS_EHIP;
-        }
-        cap = std::max(cap, emitted[0]);
-        ncap = std::max(ncap, emitted[16]);
-    }
+    r = counted_emit(
+        h, "rag block", cnt, kRedNodes + 1, kRedNodes + 1, caps, 2,
+        [&] {
+            int r;
+            if ((r = grow(h, h->rg_pairs, 2 * sizeof(uint64_t) * (size_t)caps[0].cap)) != CTWS_OK) return r;
+            if ((r = grow(h, h->rg_w, sizeof(uint64_t) * (size_t)caps[0].cap)) != CTWS_OK) return r;
+            if ((r = grow(h, h->rg_nodes, sizeof(uint64_t) * (size_t)caps[1].cap)) != CTWS_OK) return r;
+            a.pairs = (uint64_t*)h->rg_pairs.p;
+            a.weights = (uint64_t*)h->rg_w.p;
+            a.nodes = (uint64_t*)h->rg_nodes.p;
+            a.cap = caps[0].cap;
+            a.ncap = caps[1].cap;
+            k_rag_pairs<<<g, 256, 0, h->stream>>>(a);
+            return CTWS_OK;
+        },
+        [](const unsigned long long*) { return CTWS_OK; }, &e);
+    if (r != CTWS_OK) return r;
+    const int64_t n_pairs = (int64_t)e.w[kRedEmit], n_ids = (int64_t)e.w[kRedNodes];
     record(h, 1);
     // nodes: the sorted unique of the emitted ids = np.unique of the block (without 0 under
     // ignore_label: the kernel emits no 0 then)
     int64_t nt = 0;
-    if ((r = rag_table(h, (const uint64_t*)h->rg_nodes.p, (int64_t)emitted[16], &nt)) != CTWS_OK) return r;
+    if ((r = rag_table(h, (const uint64_t*)h->rg_nodes.p, n_ids, &nt)) != CTWS_OK) return r;
     const uint64_t* tab = (const uint64_t*)h->rg_tab.p;
     record(h, 7);
     HIPCHK(hipStreamSynchronize(h->stream));
-    rag_time(h, "rag_pairs", 0, 1);
-    rag_time(h, "rag_nodes", 1, 7);
-    add_timing(h, "rag_pair_passes", (float)(attempt + 1));  // (counts, as the flood's rounds)
-    add_timing(h, "rag_emits", (float)emitted[0]);
-    add_timing(h, "rag_node_emits", (float)emitted[16]);
+    stage_time(h, "rag_pairs", 0, 1);
+    stage_time(h, "rag_nodes", 1, 7);
+    add_timing(h, "rag_pair_passes", (float)e.passes);  // (counts, as the flood's rounds)
+    add_timing(h, "rag_emits", (float)n_pairs);
+    add_timing(h, "rag_node_emits", (float)n_ids);
     int64_t m = 0;
-    if ((r = pairs_tail(h, (const uint64_t*)h->rg_pairs.p, (const uint64_t*)h->rg_w.p, (int64_t)emitted[0], tab, nt,
-                        &m)) != CTWS_OK)
+    if ((r = pairs_tail(h, (const uint64_t*)h->rg_pairs.p, (const uint64_t*)h->rg_w.p, n_pairs, tab, nt, &m)) !=
+        CTWS_OK)
         return r;
     *n_nodes = nt;
     *n_edges = m;
@@ -3464,26 +3604,18 @@ int rag_block(ctws_handle* h, const uint64_t* labels, int64_t nz, int64_t ny, in
 int ctws_unique_pairs_u64(ctws_handle* h, const uint64_t* pairs, const uint64_t* weights, int64_t n, int on_device,
                           uint64_t* out, uint64_t* counts, int64_t cap, int64_t* n_unique) {
     if (!h || (!pairs && n > 0) || n < 0 || !n_unique || cap < 0 || (!out && cap > 0)) return CTWS_EINVAL;
-    h->err.clear();
-    h->timings.clear();
-    HIPCHK(hipSetDevice(h->device));
+    int r;
+    if ((r = call_begin(h)) != CTWS_OK) return r;
     *n_unique = 0;
     if (n == 0) return CTWS_OK;
     if (n >= (1ll << 30)) {
         h->err = "unique pairs: 2^30 or more pairs in one call";
         return CTWS_EUNSUPPORTED;
     }
-    int r;
-    if (!on_device) {
-        if ((r = grow(h, h->rg_pairs, 2 * sizeof(uint64_t) * (size_t)n)) != CTWS_OK) return r;
-        HIPCHK(hipMemcpyAsync(h->rg_pairs.p, pairs, 2 * sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-        pairs = (const uint64_t*)h->rg_pairs.p;
-        if (weights) {
-            if ((r = grow(h, h->rg_lab, sizeof(uint64_t) * (size_t)n)) != CTWS_OK) return r;
-            HIPCHK(hipMemcpyAsync(h->rg_lab.p, weights, sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-            weights = (const uint64_t*)h->rg_lab.p;
-        }
-    }
+    const bool dev = on_device != 0;
+    if ((r = stage_in(h, h->rg_pairs, pairs, 2 * sizeof(uint64_t) * (size_t)n, dev, &pairs)) != CTWS_OK) return r;
+    if (weights && (r = stage_in(h, h->rg_lab, weights, sizeof(uint64_t) * (size_t)n, dev, &weights)) != CTWS_OK)
+        return r;
     // ids -> ranks: the distinct endpoint values
     int64_t nt = 0;
     if ((r = rag_table(h, pairs, 2 * n, &nt)) != CTWS_OK) return r;
@@ -3519,30 +3651,18 @@ int label_overlaps(ctws_handle* h, const uint64_t* nodes_vol, const uint64_t* la
                    uint64_t ignore_label, uint64_t* rows, int64_t cap, int64_t* n_rows, bool dev) {
     if (!h || n < 0 || ((!nodes_vol || !labels_vol) && n > 0) || !n_rows || cap < 0 || (!rows && cap > 0))
         return CTWS_EINVAL;
-    h->err.clear();
-    h->timings.clear();
-    HIPCHK(hipSetDevice(h->device));
+    int r;
+    if ((r = call_begin(h)) != CTWS_OK) return r;
     *n_rows = 0;
     if (n == 0) return CTWS_OK;
-    if (n >= (1ll << 31)) {
-        h->err = "label overlaps: 2^31 or more voxels in one call (the pair kernel indexes the arrays with 32 bits)";
-        return CTWS_EUNSUPPORTED;
-    }
-    int r;
+    r = check_extent(h, 1, 1, n, "label overlaps", "call", "the pair kernel indexes the arrays with 32 bits");
+    if (r != CTWS_OK) return r;
     const size_t nb = sizeof(uint64_t) * (size_t)n;
-    const uint64_t *dn = nodes_vol, *dl = labels_vol;
-    if (!dev) {
-        if ((r = grow(h, h->rg_lab, nb)) != CTWS_OK) return r;
-        if ((r = grow(h, h->ov_lab, nb)) != CTWS_OK) return r;
-        HIPCHK(copy_pieces(h->rg_lab.p, nodes_vol, nb, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(copy_pieces(h->ov_lab.p, labels_vol, nb, hipMemcpyHostToDevice, h->stream));
-        dn = (const uint64_t*)h->rg_lab.p;
-        dl = (const uint64_t*)h->ov_lab.p;
-    }
-    // the run heads: a first buffer of a quarter of the voxels (the size depends on n alone, so a
-    // call behaves the same whatever the handle ran before); the emission is repeated with the
-    // counted size when it did not fit -- at most one emit per voxel
-    if ((r = grow(h, h->rg_red, kRagRed * sizeof(uint64_t))) != CTWS_OK) return r;
+    const uint64_t *dn, *dl;
+    if ((r = stage_in(h, h->rg_lab, nodes_vol, nb, dev, &dn)) != CTWS_OK) return r;
+    if ((r = stage_in(h, h->ov_lab, labels_vol, nb, dev, &dl)) != CTWS_OK) return r;
+    // the run heads, at most one per voxel, into a first buffer of a quarter of the voxels
+    if ((r = grow(h, h->rg_red, kRedWords * sizeof(uint64_t))) != CTWS_OK) return r;
     unsigned long long* cnt = (unsigned long long*)h->rg_red.p;
     OvArgs a;
     a.nodes = dn;
@@ -3554,32 +3674,28 @@ int label_overlaps(ctws_handle* h, const uint64_t* nodes_vol, const uint64_t* la
     const int64_t words = (n + 63) / 64;
     // four workgroups per CU, as k_rag_pairs: every wave ends with an append of its own
     const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>((words + 3) / 4, 1024));
-    unsigned long long emitted = 0;
-    unsigned long long ecap = (unsigned long long)std::max<int64_t>(64, n / 4);
+    EmitCap ecap = {kRedEmit, first_cap(n, 4)};
+    Emitted e;
     record(h, 0);
-    int attempt = 0;
-    for (; attempt < 2; ++attempt) {
-        if ((r = grow(h, h->rg_pairs, 2 * sizeof(uint64_t) * (size_t)ecap)) != CTWS_OK) return r;
-        if ((r = grow(h, h->rg_w, sizeof(uint64_t) * (size_t)ecap)) != CTWS_OK) return r;
-        a.pairs = (uint64_t*)h->rg_pairs.p;
-        a.weights = (uint64_t*)h->rg_w.p;
-        a.cap = ecap;
-        HIPCHK(hipMemsetAsync(cnt, 0, sizeof(uint64_t), h->stream));
-        k_ov_pairs<<<g, 256, 0, h->stream>>>(a);
-        LAUNCHCHK();
-        HIPCHK(hipMemcpyAsync(&emitted, cnt, sizeof(emitted), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if (emitted <= ecap) break;
-        if (attempt == 1 || emitted > (unsigned long long)n) {
-            h->err = "label overlaps: the emit count changed between two passes over the same arrays";
-            return CTWS_EHIP;
-        }
-        ecap = emitted;
-    }
+    r = counted_emit(
+        h, "label overlaps", cnt, 1, 1, &ecap, 1,
+        [&] {
+            int r;
+            if ((r = grow(h, h->rg_pairs, 2 * sizeof(uint64_t) * (size_t)ecap.cap)) != CTWS_OK) return r;
+            if ((r = grow(h, h->rg_w, sizeof(uint64_t) * (size_t)ecap.cap)) != CTWS_OK) return r;
+            a.pairs = (uint64_t*)h->rg_pairs.p;
+            a.weights = (uint64_t*)h->rg_w.p;
+            a.cap = ecap.cap;
+            k_ov_pairs<<<g, 256, 0, h->stream>>>(a);
+            return CTWS_OK;
+        },
+        [&](const unsigned long long* w) { return runs_within(h, "label overlaps", w[kRedEmit], 0, n); }, &e);
+    if (r != CTWS_OK) return r;
+    const unsigned long long emitted = e.w[kRedEmit];
     record(h, 1);
     HIPCHK(hipStreamSynchronize(h->stream));
-    rag_time(h, "ov_pairs", 0, 1);
-    add_timing(h, "ov_pair_passes", (float)(attempt + 1));  // (counts, as the flood's rounds)
+    stage_time(h, "ov_pairs", 0, 1);
+    add_timing(h, "ov_pair_passes", (float)e.passes);  // (counts, as the flood's rounds)
     add_timing(h, "ov_emits", (float)emitted);
     if (emitted == 0) return CTWS_OK;  // every voxel carries the ignore label
     if (emitted >= (1ull << 30)) {
@@ -3591,7 +3707,7 @@ int label_overlaps(ctws_handle* h, const uint64_t* nodes_vol, const uint64_t* la
     if ((r = rag_table(h, (const uint64_t*)h->rg_pairs.p, 2 * (int64_t)emitted, &nt)) != CTWS_OK) return r;
     record(h, 7);
     HIPCHK(hipStreamSynchronize(h->stream));
-    rag_time(h, "ov_table", 1, 7);
+    stage_time(h, "ov_table", 1, 7);
     if ((r = pairs_tail(h, (const uint64_t*)h->rg_pairs.p, (const uint64_t*)h->rg_w.p, (int64_t)emitted,
                         (const uint64_t*)h->rg_tab.p, nt, &m)) != CTWS_OK)
         return r;
@@ -3601,17 +3717,12 @@ int label_overlaps(ctws_handle* h, const uint64_t* nodes_vol, const uint64_t* la
         return CTWS_EINVAL;
     }
     const size_t rb = 3 * sizeof(uint64_t) * (size_t)m;
-    uint64_t* drows = rows;
-    if (!dev) {
-        if ((r = grow(h, h->ov_rows, rb)) != CTWS_OK) return r;
-        drows = (uint64_t*)h->ov_rows.p;
-    }
+    uint64_t* drows;
+    if ((r = out_begin(h, h->ov_rows, rows, rb, dev, &drows)) != CTWS_OK) return r;
     const unsigned gm = (unsigned)std::min<int64_t>((m + 255) / 256, 8192);
     k_ov_rows<<<gm, 256, 0, h->stream>>>((const uint64_t*)h->rg_out.p, (const uint64_t*)h->rg_sum.p, m, drows);
     LAUNCHCHK();
-    if (!dev) HIPCHK(hipMemcpyAsync(rows, drows, rb, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return CTWS_OK;
+    return out_end(h, rows, drows, rb, dev);
 }
 }  // namespace
 }  // extern "C++"
@@ -3633,25 +3744,22 @@ int block_morphology(ctws_handle* h, const uint64_t* labels, int64_t nz, int64_t
                      double* rows, int64_t cap, int64_t* n_rows, bool dev) {
     if (!h || !labels || nz <= 0 || ny <= 0 || nx <= 0 || !begin || !n_rows || cap < 0 || (!rows && cap > 0))
         return CTWS_EINVAL;
-    h->err.clear();
-    h->timings.clear();
+    int r;
+    if ((r = call_begin(h)) != CTWS_OK) return r;
     *n_rows = 0;
     if (begin[0] < 0 || begin[1] < 0 || begin[2] < 0) {
         h->err = "block morphology: a negative begin";
         return CTWS_EINVAL;
     }
-    HIPCHK(hipSetDevice(h->device));
     // the record packs z, y, x0 into 19 bits each; begin + extent <= 2^21 and fewer than 2^31
     // voxels keep every coordinate sum below 2^52, exact in a double
-    constexpr int64_t kExt = 1ll << 19, kCoord = 1ll << 21, kMax = 1ll << 31;
+    constexpr int64_t kExt = 1ll << 19, kCoord = 1ll << 21;
     if (nz >= kExt || ny >= kExt || nx >= kExt) {
         h->err = "block morphology: an extent of 2^19 or more (the run record holds 19 bits per coordinate)";
         return CTWS_EUNSUPPORTED;
     }
-    if (nz * ny >= kMax || nz * ny * nx >= kMax) {
-        h->err = "block morphology: 2^31 or more voxels in one block (the run kernel indexes a block with 32 bits)";
-        return CTWS_EUNSUPPORTED;
-    }
+    r = check_extent(h, nz, ny, nx, "block morphology", "block", "the run kernel indexes a block with 32 bits");
+    if (r != CTWS_OK) return r;
     const int64_t ext[3] = {nz, ny, nx};
     for (int d = 0; d < 3; ++d)
         if (begin[d] > kCoord || begin[d] + ext[d] > kCoord) {
@@ -3659,18 +3767,11 @@ int block_morphology(ctws_handle* h, const uint64_t* labels, int64_t nz, int64_t
             return CTWS_EUNSUPPORTED;
         }
     const int64_t N = nz * ny * nx;
-    int r;
-    const uint64_t* dl = labels;
-    if (!dev) {
-        if ((r = grow(h, h->rg_lab, sizeof(uint64_t) * (size_t)N)) != CTWS_OK) return r;
-        HIPCHK(copy_pieces(h->rg_lab.p, labels, sizeof(uint64_t) * (size_t)N, hipMemcpyHostToDevice, h->stream));
-        dl = (const uint64_t*)h->rg_lab.p;
-    }
-    // the run heads: a first buffer of a quarter of the voxels (the size depends on the block
-    // alone, so a call behaves the same whatever the handle ran before); the emission is repeated
-    // with the counted size when it did not fit -- at most one emit per voxel
-    if ((r = grow(h, h->rg_red, kRagRed * sizeof(uint64_t))) != CTWS_OK) return r;
-    // [0] the append counter on a 128-B line of its own, [16] the largest id, [19] runs
+    const uint64_t* dl;
+    if ((r = stage_in(h, h->rg_lab, labels, sizeof(uint64_t) * (size_t)N, dev, &dl)) != CTWS_OK) return r;
+    // the run heads, at least one and at most one per voxel, into a first buffer of a quarter of
+    // the voxels
+    if ((r = grow(h, h->rg_red, kRedWords * sizeof(uint64_t))) != CTWS_OK) return r;
     unsigned long long* cnt = (unsigned long long*)h->rg_red.p;
     MorphArgs a;
     a.lab = dl;
@@ -3678,88 +3779,45 @@ int block_morphology(ctws_handle* h, const uint64_t* labels, int64_t nz, int64_t
     a.ny = (uint32_t)ny;
     a.nx = (uint32_t)nx;
     a.count = cnt;
-    a.vmax = cnt + 16;
+    a.vmax = cnt + kRedVmax;
     const int64_t lines = nz * ny;
     // four workgroups per CU, as k_rag_pairs: every wave ends with an append of its own
     const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>((lines + 3) / 4, 1024));
-    unsigned long long emitted = 0;
-    unsigned long long got[17] = {0};
-    unsigned long long ecap = (unsigned long long)std::max<int64_t>(64, N / 4);
+    EmitCap ecap = {kRedEmit, first_cap(N, 4)};
+    Emitted e;
     record(h, 0);
-    int attempt = 0;
-    for (; attempt < 2; ++attempt) {
-        if ((r = grow(h, h->rg_pairs, sizeof(uint64_t) * (size_t)ecap)) != CTWS_OK) return r;
-        if ((r = grow(h, h->rg_w, sizeof(uint64_t) * (size_t)ecap)) != CTWS_OK) return r;
-        a.ids = (uint64_t*)h->rg_pairs.p;
-        a.recs = (uint64_t*)h->rg_w.p;
-        a.cap = ecap;
-        HIPCHK(hipMemsetAsync(cnt, 0, 17 * sizeof(uint64_t), h->stream));
-        k_morph_runs<<<g, 256, 0, h->stream>>>(a);
-        LAUNCHCHK();
-        HIPCHK(hipMemcpyAsync(got, cnt, sizeof(got), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        emitted = got[0];
-        if (emitted <= ecap) break;
-        if (attempt == 1 || emitted > (unsigned long long)N) {
-            h->err = "block morphology: the emit count changed between two passes over the same labels";
-            return CTWS_EHIP;
-        }
-        ecap = emitted;
-    }
-    if (emitted == 0 || emitted > (unsigned long long)N) {
-        h->err = "block morphology: the run kernel counted " + std::to_string(emitted) + " runs";
-        return CTWS_EHIP;
-    }
-    const int64_t n = (int64_t)emitted;  // (< 2^31)
+    r = counted_emit(
+        h, "block morphology", cnt, kRedVmax + 1, kRedVmax + 1, &ecap, 1,
+        [&] {
+            int r;
+            if ((r = grow(h, h->rg_pairs, sizeof(uint64_t) * (size_t)ecap.cap)) != CTWS_OK) return r;
+            if ((r = grow(h, h->rg_w, sizeof(uint64_t) * (size_t)ecap.cap)) != CTWS_OK) return r;
+            a.ids = (uint64_t*)h->rg_pairs.p;
+            a.recs = (uint64_t*)h->rg_w.p;
+            a.cap = ecap.cap;
+            k_morph_runs<<<g, 256, 0, h->stream>>>(a);
+            return CTWS_OK;
+        },
+        [&](const unsigned long long* w) { return runs_within(h, "block morphology", w[kRedEmit], 1, N); }, &e);
+    if (r != CTWS_OK) return r;
+    const int64_t n = (int64_t)e.w[kRedEmit];  // (< 2^31)
     record(h, 1);
-    // the largest id (taken by the run pass): the sort's bits, and the 2^53 limit of the id column
-    const unsigned long long vmax = got[16];
-    if (vmax >= (1ull << 53)) {
-        h->err = "block morphology: an id of 2^53 or more (" + std::to_string(vmax) +
-                 ") has no exact place in the float64 table";
-        return CTWS_EUNSUPPORTED;
-    }
-    int bits = 1;
-    while (bits < 53 && (1ull << bits) <= vmax) ++bits;
-    const size_t nb = sizeof(uint64_t) * (size_t)n;
-    size_t tb_sort = 0, tb_rle = 0;
-    HIPCHK(pair_sort(nullptr, tb_sort, nullptr, nullptr, nullptr, nullptr, n, bits, h->stream));
-    HIPCHK(u64_runs(nullptr, tb_rle, nullptr, nullptr, nullptr, nullptr, n, h->stream));
-    if ((r = grow(h, h->rg_skeys, nb)) != CTWS_OK) return r;
-    if ((r = grow(h, h->rg_sw, nb)) != CTWS_OK) return r;
-    if ((r = grow(h, h->rg_keys, nb)) != CTWS_OK) return r;
-    if ((r = grow(h, h->rg_sum, nb)) != CTWS_OK) return r;
-    if ((r = grow(h, h->rg_tmp, std::max(tb_sort, tb_rle))) != CTWS_OK) return r;
-    uint64_t* sids = (uint64_t*)h->rg_skeys.p;
-    uint64_t* srecs = (uint64_t*)h->rg_sw.p;
-    uint64_t* uniq = (uint64_t*)h->rg_keys.p;
-    uint64_t* counts = (uint64_t*)h->rg_sum.p;
-    HIPCHK(pair_sort(h->rg_tmp.p, tb_sort, a.ids, sids, a.recs, srecs, n, bits, h->stream));
-    HIPCHK(u64_runs(h->rg_tmp.p, tb_rle, sids, uniq, counts, (uint64_t*)(cnt + 19), n, h->stream));
-    record(h, 2);
-    unsigned long long runs = 0;
-    HIPCHK(hipMemcpyAsync(&runs, cnt + 19, sizeof(runs), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    rag_time(h, "morph_runs", 0, 1);
-    rag_time(h, "morph_sort", 1, 2);
-    add_timing(h, "morph_run_passes", (float)(attempt + 1));  // (counts, as the flood's rounds)
-    add_timing(h, "morph_emits", (float)emitted);
-    if (runs == 0 || runs > emitted) {
-        h->err = "block morphology: " + std::to_string(runs) + " ids from " + std::to_string(emitted) + " runs";
-        return CTWS_EHIP;
-    }
-    const int64_t m = (int64_t)runs;
+    // the largest id was taken by the run pass
+    ById s;
+    if ((r = sort_by_id(h, "block morphology", a.ids, a.recs, n, e.w[kRedVmax], 2, &s)) != CTWS_OK) return r;
+    stage_time(h, "morph_runs", 0, 1);
+    stage_time(h, "morph_sort", 1, 2);
+    add_timing(h, "morph_run_passes", (float)e.passes);  // (counts, as the flood's rounds)
+    add_timing(h, "morph_emits", (float)n);
+    const int64_t m = s.m;
     *n_rows = m;
     if (m > cap) {
         h->err = "block morphology: output capacity too small";
         return CTWS_EINVAL;
     }
     const size_t rb = 11 * sizeof(double) * (size_t)m;
-    double* drows = rows;
-    if (!dev) {
-        if ((r = grow(h, h->mo_rows, rb)) != CTWS_OK) return r;
-        drows = (double*)h->mo_rows.p;
-    }
+    double* drows;
+    if ((r = out_begin(h, h->mo_rows, rows, rb, dev, &drows)) != CTWS_OK) return r;
     // the per-id table of the split segments: ten integers per id, zero = neutral
     const size_t ab = 10 * sizeof(uint64_t) * (size_t)m;
     if ((r = grow(h, h->mo_acc, ab)) != CTWS_OK) return r;
@@ -3768,17 +3826,16 @@ int block_morphology(ctws_handle* h, const uint64_t* labels, int64_t nz, int64_t
     const MorphBegin b = {(uint64_t)begin[0], (uint64_t)begin[1], (uint64_t)begin[2]};
     const int64_t waves = m + n / kMorphChunk;  // a wave per id and per whole chunk of records
     const unsigned gm = (unsigned)std::max<int64_t>(1, std::min<int64_t>((waves + 3) / 4, 2048));
-    k_morph_rows<<<gm, 256, 0, h->stream>>>(sids, srecs, (uint32_t)n, uniq, counts, (uint32_t)m, b, acc, drows);
+    k_morph_rows<<<gm, 256, 0, h->stream>>>(s.sids, s.srecs, (uint32_t)n, s.uniq, s.counts, (uint32_t)m, b, acc, drows);
     LAUNCHCHK();
     if (n >= (int64_t)kMorphChunk) {  // (a shorter record list holds no whole chunk: no split segment)
         const unsigned gl = (unsigned)std::min<int64_t>((m + 255) / 256, 1024);
-        k_morph_long_rows<<<gl, 256, 0, h->stream>>>(uniq, (uint32_t)m, b, acc, drows);
+        k_morph_long_rows<<<gl, 256, 0, h->stream>>>(s.uniq, (uint32_t)m, b, acc, drows);
         LAUNCHCHK();
     }
     record(h, 3);
-    if (!dev) HIPCHK(hipMemcpyAsync(rows, drows, rb, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    rag_time(h, "morph_rows", 2, 3);
+    if ((r = out_end(h, rows, drows, rb, dev)) != CTWS_OK) return r;
+    stage_time(h, "morph_rows", 2, 3);
     return CTWS_OK;
 }
 }  // namespace
@@ -3802,38 +3859,27 @@ int region_features_block(ctws_handle* h, const uint64_t* labels, const void* da
                           int64_t* n_rows, bool dev) {
     if (!h || !labels || !data || nz <= 0 || ny <= 0 || nx <= 0 || !n_rows || cap < 0 || (!rows && cap > 0))
         return CTWS_EINVAL;
-    h->err.clear();
-    h->timings.clear();
+    int r;
+    if ((r = call_begin(h)) != CTWS_OK) return r;
     *n_rows = 0;
     if (data_dtype != CTWS_U8 && data_dtype != CTWS_U16 && data_dtype != CTWS_F32 && data_dtype != CTWS_F64) {
         h->err = "region features: the input map is uint8, uint16, float32 or float64";
         return CTWS_EINVAL;
     }
-    HIPCHK(hipSetDevice(h->device));
-    constexpr int64_t kMax = 1ll << 31;
-    if (nz >= kMax || ny >= kMax || nx >= kMax || nz * ny >= kMax || nz * ny * nx >= kMax) {
-        h->err = "region features: 2^31 or more voxels in one block (the kernels index a block with 32 bits)";
-        return CTWS_EUNSUPPORTED;
-    }
+    r = check_extent(h, nz, ny, nx, "region features", "block", "the kernels index a block with 32 bits");
+    if (r != CTWS_OK) return r;
     const int64_t N = nz * ny * nx, lines = nz * ny;
-    if (lines + 1 >= kMax) {  // (the scan takes the rows' counts and one 0 behind them with a 32-bit size)
+    if (lines + 1 >= (1ll << 31)) {  // (the scan takes the rows' counts and one 0 behind them with a 32-bit size)
         h->err = "region features: 2^31 - 1 rows in one block (the scan of the rows' run counts is 32-bit)";
         return CTWS_EUNSUPPORTED;
     }
     const size_t es = data_dtype == CTWS_U8 ? 1 : data_dtype == CTWS_U16 ? 2 : data_dtype == CTWS_F32 ? 4 : 8;
-    int r;
-    const uint64_t* dl = labels;
-    const void* dd = data;
-    if (!dev) {
-        if ((r = grow(h, h->rg_lab, sizeof(uint64_t) * (size_t)N)) != CTWS_OK) return r;
-        if ((r = grow(h, h->rf_data, es * (size_t)N)) != CTWS_OK) return r;
-        HIPCHK(copy_pieces(h->rg_lab.p, labels, sizeof(uint64_t) * (size_t)N, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(copy_pieces(h->rf_data.p, data, es * (size_t)N, hipMemcpyHostToDevice, h->stream));
-        dl = (const uint64_t*)h->rg_lab.p;
-        dd = h->rf_data.p;
-    }
-    if ((r = grow(h, h->rg_red, kRagRed * sizeof(uint64_t))) != CTWS_OK) return r;
-    unsigned long long* red = (unsigned long long*)h->rg_red.p;  // [16] the largest id, [19] the ids' number
+    const uint64_t* dl;
+    const void* dd;
+    if ((r = stage_in(h, h->rg_lab, labels, sizeof(uint64_t) * (size_t)N, dev, &dl)) != CTWS_OK) return r;
+    if ((r = stage_in(h, h->rf_data, data, es * (size_t)N, dev, &dd)) != CTWS_OK) return r;
+    if ((r = grow(h, h->rg_red, kRedWords * sizeof(uint64_t))) != CTWS_OK) return r;
+    unsigned long long* red = (unsigned long long*)h->rg_red.p;
     // the rows' run counts with one 0 behind them: the scan's last entry is the total
     const size_t cb = sizeof(uint32_t) * (size_t)(lines + 1);
     size_t tb_scan = 0;
@@ -3847,7 +3893,7 @@ int region_features_block(ctws_handle* h, const uint64_t* labels, const void* da
     const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>((lines + 3) / 4, 1024));
     record(h, 0);
     HIPCHK(hipMemsetAsync(rcnt + lines, 0, sizeof(uint32_t), h->stream));
-    HIPCHK(hipMemsetAsync(red, 0, kRagRed * sizeof(uint64_t), h->stream));
+    HIPCHK(hipMemsetAsync(red, 0, kRedWords * sizeof(uint64_t), h->stream));
     k_regfeat_count<<<g, 256, 0, h->stream>>>(dl, (uint32_t)lines, (uint32_t)nx, rcnt);
     LAUNCHCHK();
     HIPCHK(u32_exclusive_sum(h->rg_tmp.p, tb_scan, rcnt, roff, lines + 1, h->stream));
@@ -3876,62 +3922,31 @@ int region_features_block(ctws_handle* h, const uint64_t* labels, const void* da
     a.ids = (uint64_t*)h->rg_pairs.p;
     a.vals = (uint64_t*)h->rg_w.p;
     a.sums = (double*)h->rf_sums.p;
-    a.vmax = red + 16;
+    a.vmax = red + kRedVmax;
     if (data_dtype == CTWS_U8) k_regfeat_runs<uint8_t><<<g, 256, 0, h->stream>>>(a);
     else if (data_dtype == CTWS_U16) k_regfeat_runs<uint16_t><<<g, 256, 0, h->stream>>>(a);
     else if (data_dtype == CTWS_F32) k_regfeat_runs<float><<<g, 256, 0, h->stream>>>(a);
     else k_regfeat_runs<double><<<g, 256, 0, h->stream>>>(a);
     LAUNCHCHK();
     record(h, 2);
-    // the largest id: the sort's bits, and the 2^53 limit of the id column
-    unsigned long long vmax = 0;
-    HIPCHK(hipMemcpyAsync(&vmax, red + 16, sizeof(vmax), hipMemcpyDeviceToHost, h->stream));
+    unsigned long long vmax = 0;  // the largest id
+    HIPCHK(hipMemcpyAsync(&vmax, red + kRedVmax, sizeof(vmax), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (vmax >= (1ull << 53)) {
-        h->err = "region features: an id of 2^53 or more (" + std::to_string(vmax) +
-                 ") has no exact place in the float64 rows";
-        return CTWS_EUNSUPPORTED;
-    }
-    int bits = 1;
-    while (bits < 53 && (1ull << bits) <= vmax) ++bits;
-    size_t tb_sort = 0, tb_rle = 0;
-    HIPCHK(pair_sort(nullptr, tb_sort, nullptr, nullptr, nullptr, nullptr, n, bits, h->stream));
-    HIPCHK(u64_runs(nullptr, tb_rle, nullptr, nullptr, nullptr, nullptr, n, h->stream));
-    if ((r = grow(h, h->rg_skeys, nb)) != CTWS_OK) return r;
-    if ((r = grow(h, h->rg_sw, nb)) != CTWS_OK) return r;
-    if ((r = grow(h, h->rg_keys, nb)) != CTWS_OK) return r;
-    if ((r = grow(h, h->rg_sum, nb)) != CTWS_OK) return r;
-    if ((r = grow(h, h->rg_tmp, std::max(tb_sort, tb_rle))) != CTWS_OK) return r;
-    uint64_t* sids = (uint64_t*)h->rg_skeys.p;
-    uint64_t* svals = (uint64_t*)h->rg_sw.p;
-    uint64_t* uniq = (uint64_t*)h->rg_keys.p;
-    uint64_t* counts = (uint64_t*)h->rg_sum.p;
-    HIPCHK(pair_sort(h->rg_tmp.p, tb_sort, a.ids, sids, a.vals, svals, n, bits, h->stream));
-    HIPCHK(u64_runs(h->rg_tmp.p, tb_rle, sids, uniq, counts, (uint64_t*)(red + 19), n, h->stream));
-    record(h, 3);
-    unsigned long long runs = 0;
-    HIPCHK(hipMemcpyAsync(&runs, red + 19, sizeof(runs), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    rag_time(h, "regfeat_count", 0, 1);
-    rag_time(h, "regfeat_runs", 1, 2);
-    rag_time(h, "regfeat_sort", 2, 3);
+    ById s;
+    if ((r = sort_by_id(h, "region features", a.ids, a.vals, n, vmax, 3, &s)) != CTWS_OK) return r;
+    stage_time(h, "regfeat_count", 0, 1);
+    stage_time(h, "regfeat_runs", 1, 2);
+    stage_time(h, "regfeat_sort", 2, 3);
     add_timing(h, "regfeat_records", (float)total);  // (a count, as the flood's rounds)
-    if (runs == 0 || runs > (unsigned long long)n) {
-        h->err = "region features: " + std::to_string(runs) + " ids from " + std::to_string(n) + " runs";
-        return CTWS_EHIP;
-    }
-    const int64_t m = (int64_t)runs;
+    const int64_t m = s.m;
     *n_rows = m;
     if (m > cap) {
         h->err = "region features: output capacity too small";
         return CTWS_EINVAL;
     }
     const size_t rb = 3 * sizeof(double) * (size_t)m;
-    double* drows = rows;
-    if (!dev) {
-        if ((r = grow(h, h->rf_rows, rb)) != CTWS_OK) return r;
-        drows = (double*)h->rf_rows.p;
-    }
+    double* drows;
+    if ((r = out_begin(h, h->rf_rows, rows, rb, dev, &drows)) != CTWS_OK) return r;
     // the chunk table: (n, sum) per whole aligned chunk of sorted records, the n first
     const int64_t chunks = n / kRegfeatChunk;
     if ((r = grow(h, h->rf_ctab, 2 * sizeof(uint64_t) * (size_t)std::max<int64_t>(1, chunks))) != CTWS_OK) return r;
@@ -3939,17 +3954,16 @@ int region_features_block(ctws_handle* h, const uint64_t* labels, const void* da
     double* chunk_s = (double*)(chunk_n + std::max<int64_t>(1, chunks));
     if (chunks > 0) {
         const unsigned gc = (unsigned)std::min<int64_t>((chunks + 3) / 4, 2048);
-        k_regfeat_chunks<<<gc, 256, 0, h->stream>>>(sids, svals, a.sums, total, chunk_n, chunk_s);
+        k_regfeat_chunks<<<gc, 256, 0, h->stream>>>(s.sids, s.srecs, a.sums, total, chunk_n, chunk_s);
         LAUNCHCHK();
     }
     const unsigned gm = (unsigned)std::max<int64_t>(1, std::min<int64_t>((m + 3) / 4, 2048));
-    k_regfeat_rows<<<gm, 256, 0, h->stream>>>(sids, svals, a.sums, total, uniq, counts, (uint32_t)m, chunk_n, chunk_s,
-                                              drows);
+    k_regfeat_rows<<<gm, 256, 0, h->stream>>>(s.sids, s.srecs, a.sums, total, s.uniq, s.counts, (uint32_t)m, chunk_n,
+                                              chunk_s, drows);
     LAUNCHCHK();
     record(h, 4);
-    if (!dev) HIPCHK(hipMemcpyAsync(rows, drows, rb, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    rag_time(h, "regfeat_rows", 3, 4);
+    if ((r = out_end(h, rows, drows, rb, dev)) != CTWS_OK) return r;
+    stage_time(h, "regfeat_rows", 3, 4);
     return CTWS_OK;
 }
 }  // namespace
@@ -3985,9 +3999,9 @@ DsKernel ds_kernel(int func, int variant) {  // variant 0: any factor, 1: (1, 2,
 int downscale_block(ctws_handle* h, const void* input, int dtype, int64_t nz, int64_t ny, int64_t nx,
                     const int64_t factors[3], int func, void* out, int64_t oz, int64_t oy, int64_t ox,
                     int* any_nonzero, bool dev) {
+    int r;
     if (!h) return CTWS_EINVAL;
-    h->err.clear();
-    h->timings.clear();
+    if ((r = call_begin(h)) != CTWS_OK) return r;
     if (!input || !out || !factors || !any_nonzero || nz <= 0 || ny <= 0 || nx <= 0) {
         h->err = "downscale: bad arguments (a non-empty 3-D block, factors, an output and a flag)";
         return CTWS_EINVAL;
@@ -4006,11 +4020,8 @@ int downscale_block(ctws_handle* h, const void* input, int dtype, int64_t nz, in
             h->err = "downscale: every factor lies in 1..8";
             return CTWS_EINVAL;
         }
-    constexpr int64_t kMax = 1ll << 31;
-    if (nz >= kMax || ny >= kMax || nx >= kMax || nz * ny >= kMax || nz * ny * nx >= kMax) {
-        h->err = "downscale: 2^31 or more voxels in one block (the kernels index a block with 32 bits)";
-        return CTWS_EUNSUPPORTED;
-    }
+    r = check_extent(h, nz, ny, nx, "downscale", "block", "the kernels index a block with 32 bits");
+    if (r != CTWS_OK) return r;
     const int64_t fz = factors[0], fy = factors[1], fx = factors[2], n = fz * fy * fx;
     if (oz != (nz + fz - 1) / fz || oy != (ny + fy - 1) / fy || ox != (nx + fx - 1) / fx) {
         h->err = "downscale: the output extents are ceil(n / f) per axis";
@@ -4021,19 +4032,12 @@ int downscale_block(ctws_handle* h, const void* input, int dtype, int64_t nz, in
                  "float32 no longer holds it exactly and the reference's summation order would decide the result";
         return CTWS_EUNSUPPORTED;
     }
-    HIPCHK(hipSetDevice(h->device));
     const size_t es = dtype == CTWS_U8 ? 1 : dtype == CTWS_U16 ? 2 : dtype == CTWS_F32 ? 4 : 8;
     const int64_t N = nz * ny * nx, M = oz * oy * ox;
-    int r;
-    const void* din = input;
-    void* dout = out;
-    if (!dev) {
-        if ((r = grow(h, h->ds_in, es * (size_t)N)) != CTWS_OK) return r;
-        if ((r = grow(h, h->ds_out, es * (size_t)M)) != CTWS_OK) return r;
-        HIPCHK(copy_pieces(h->ds_in.p, input, es * (size_t)N, hipMemcpyHostToDevice, h->stream));
-        din = h->ds_in.p;
-        dout = h->ds_out.p;
-    }
+    const void* din;
+    void* dout;
+    if ((r = stage_in(h, h->ds_in, input, es * (size_t)N, dev, &din)) != CTWS_OK) return r;
+    if ((r = out_begin(h, h->ds_out, out, es * (size_t)M, dev, &dout)) != CTWS_OK) return r;
     constexpr size_t kFlagBytes = sizeof(uint32_t) * kDsFlagSlots * kDsFlagStride;
     if ((r = grow(h, h->ds_flag, kFlagBytes)) != CTWS_OK) return r;
     DownscaleArgs a;
@@ -4065,12 +4069,11 @@ int downscale_block(ctws_handle* h, const void* input, int dtype, int64_t nz, in
     record(h, 1);
     h->ds_flags.resize((size_t)kDsFlagSlots * kDsFlagStride);
     HIPCHK(hipMemcpyAsync(h->ds_flags.data(), a.flag, kFlagBytes, hipMemcpyDeviceToHost, h->stream));
-    if (!dev) HIPCHK(copy_pieces(out, dout, es * (size_t)M, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    if ((r = out_end(h, out, dout, es * (size_t)M, dev)) != CTWS_OK) return r;
     uint32_t flag = 0;
     for (int k = 0; k < kDsFlagSlots; ++k) flag |= h->ds_flags[(size_t)k * kDsFlagStride];
     *any_nonzero = flag ? 1 : 0;
-    rag_time(h, "downscale", 0, 1);
+    stage_time(h, "downscale", 0, 1);
     return CTWS_OK;
 }
 }  // namespace
@@ -4095,9 +4098,9 @@ int edge_features_block(ctws_handle* h, const uint64_t* labels, const void* data
                         int64_t ny, int64_t nx, int64_t cz, int64_t cy, int64_t cx, int ignore_label,
                         const uint64_t* nodes, int64_t n_nodes, const uint64_t* edges, int64_t n_edges, double* out,
                         int64_t* n_missing, bool dev) {
+    int r;
     if (!h) return CTWS_EINVAL;
-    h->err.clear();
-    h->timings.clear();
+    if ((r = call_begin(h)) != CTWS_OK) return r;
     if (n_missing) *n_missing = 0;
     if (!labels || !data || nz <= 0 || ny <= 0 || nx <= 0 || cz <= 0 || cy <= 0 || cx <= 0 || cz > nz || cy > ny ||
         cx > nx || n_nodes < 0 || n_edges < 0 || (n_edges > 0 && (!nodes || !edges || !out || n_nodes == 0))) {
@@ -4108,54 +4111,36 @@ int edge_features_block(ctws_handle* h, const uint64_t* labels, const void* data
         h->err = "edge features: the boundary map is float32 or uint8";
         return CTWS_EUNSUPPORTED;
     }
-    HIPCHK(hipSetDevice(h->device));
     if (n_edges == 0) return CTWS_OK;  // nothing to accumulate into: no launch
-    constexpr int64_t kMax = 1ll << 31;
-    if (nz >= kMax || ny >= kMax || nx >= kMax || nz * ny >= kMax || nz * ny * nx >= kMax) {
-        h->err = "edge features: 2^31 or more voxels in one block (the sample kernel indexes a block with 32 bits)";
-        return CTWS_EUNSUPPORTED;
-    }
+    r = check_extent(h, nz, ny, nx, "edge features", "block", "the sample kernel indexes a block with 32 bits");
+    if (r != CTWS_OK) return r;
     if (n_nodes >= (1ll << 32) || n_edges >= (1ll << 32)) {
         h->err = "edge features: 2^32 or more nodes or edges in one block";
         return CTWS_EUNSUPPORTED;
     }
     const int64_t N = nz * ny * nx;
     const size_t es = data_dtype == CTWS_U8 ? 1 : 4;
-    int r;
-    const uint64_t *dl = labels, *dn = nodes, *de = edges;
-    const void* dd = data;
-    double* dout = out;
+    const uint64_t *dl, *dn, *de;
+    const void* dd;
+    double* dout;
     const size_t out_bytes = 10 * sizeof(double) * (size_t)n_edges;
-    if (!dev) {
-        if ((r = grow(h, h->ef_lab, sizeof(uint64_t) * (size_t)N)) != CTWS_OK) return r;
-        if ((r = grow(h, h->ef_data, es * (size_t)N)) != CTWS_OK) return r;
-        if ((r = grow(h, h->ef_nodes, sizeof(uint64_t) * (size_t)n_nodes)) != CTWS_OK) return r;
-        if ((r = grow(h, h->ef_edges, 2 * sizeof(uint64_t) * (size_t)n_edges)) != CTWS_OK) return r;
-        if ((r = grow(h, h->ef_out, out_bytes)) != CTWS_OK) return r;
-        HIPCHK(copy_pieces(h->ef_lab.p, labels, sizeof(uint64_t) * (size_t)N, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(copy_pieces(h->ef_data.p, data, es * (size_t)N, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(h->ef_nodes.p, nodes, sizeof(uint64_t) * (size_t)n_nodes, hipMemcpyHostToDevice,
-                              h->stream));
-        HIPCHK(hipMemcpyAsync(h->ef_edges.p, edges, 2 * sizeof(uint64_t) * (size_t)n_edges, hipMemcpyHostToDevice,
-                              h->stream));
-        dl = (const uint64_t*)h->ef_lab.p;
-        dd = h->ef_data.p;
-        dn = (const uint64_t*)h->ef_nodes.p;
-        de = (const uint64_t*)h->ef_edges.p;
-        dout = (double*)h->ef_out.p;
-    }
+    if ((r = stage_in(h, h->ef_lab, labels, sizeof(uint64_t) * (size_t)N, dev, &dl)) != CTWS_OK) return r;
+    if ((r = stage_in(h, h->ef_data, data, es * (size_t)N, dev, &dd)) != CTWS_OK) return r;
+    if ((r = stage_in(h, h->ef_nodes, nodes, sizeof(uint64_t) * (size_t)n_nodes, dev, &dn)) != CTWS_OK) return r;
+    if ((r = stage_in(h, h->ef_edges, edges, 2 * sizeof(uint64_t) * (size_t)n_edges, dev, &de)) != CTWS_OK) return r;
+    if ((r = out_begin(h, h->ef_out, out, out_bytes, dev, &dout)) != CTWS_OK) return r;
     int b = 1;  // bits per rank
     while ((1ll << b) < n_nodes) ++b;
     int eb = 1;  // bits per edge index
     while ((1ll << eb) < n_edges) ++eb;
-    // counters: [0] the append counter on a 128-B line of its own, [16] missing pairs, [17] bad edges
-    if ((r = grow(h, h->ef_red, 32 * sizeof(uint64_t))) != CTWS_OK) return r;
+    if ((r = grow(h, h->ef_red, kRedWords * sizeof(uint64_t))) != CTWS_OK) return r;
     if ((r = grow(h, h->ef_ekeys, sizeof(uint64_t) * (size_t)n_edges)) != CTWS_OK) return r;
     unsigned long long* cnt = (unsigned long long*)h->ef_red.p;
-    HIPCHK(hipMemsetAsync(cnt, 0, 32 * sizeof(uint64_t), h->stream));
+    HIPCHK(hipMemsetAsync(cnt, 0, kRedWords * sizeof(uint64_t), h->stream));
     record(h, 0);
     const unsigned ge = (unsigned)std::min<int64_t>((n_edges + 255) / 256, 8192);
-    k_ef_edge_keys<<<ge, 256, 0, h->stream>>>(de, n_edges, dn, n_nodes, b, (uint64_t*)h->ef_ekeys.p, cnt + 17);
+    k_ef_edge_keys<<<ge, 256, 0, h->stream>>>(de, n_edges, dn, n_nodes, b, (uint64_t*)h->ef_ekeys.p,
+                                              cnt + kRedBadEdges);
     LAUNCHCHK();
     record(h, 1);
     EfArgs a;
@@ -4174,44 +4159,40 @@ int edge_features_block(ctws_handle* h, const uint64_t* labels, const void* data
     a.ekeys = (const uint64_t*)h->ef_ekeys.p;
     a.ne = (uint32_t)n_edges;
     a.count = cnt;
-    a.missing = cnt + 16;
+    a.missing = cnt + kRedMissing;
     const int64_t rows = cz * cy;
     // the grid of k_rag_pairs: four workgroups per CU, every wave ends with an append of its own
     const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>((rows + 3) / 4, 1024));
-    // first capacity: half a key per voxel (a block of fragments emits ~0.38), a function of the
-    // block alone; the pass is repeated at the counted size when it did not fit
-    unsigned long long cap = (unsigned long long)std::max<int64_t>(64, N / 2);
-    unsigned long long res[18] = {0};
-    int attempt = 0;
-    for (; attempt < 2; ++attempt) {
-        if ((r = grow(h, h->ef_keys, sizeof(uint64_t) * (size_t)cap)) != CTWS_OK) return r;
-        a.keys = (uint64_t*)h->ef_keys.p;
-        a.cap = cap;
-        HIPCHK(hipMemsetAsync(cnt, 0, 17 * sizeof(uint64_t), h->stream));  // (not the bad-edge count)
-        if (data_dtype == CTWS_U8) k_ef_samples<uint8_t><<<g, 256, 0, h->stream>>>(a);
-        else k_ef_samples<float><<<g, 256, 0, h->stream>>>(a);
-        LAUNCHCHK();
-        HIPCHK(hipMemcpyAsync(res, cnt, sizeof(res), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if (res[17]) {
-            h->err = "edge features: " + std::to_string(res[17]) +
+    // first capacity: half a key per voxel (a block of fragments emits ~0.38).  The bad-edge
+    // count of k_ef_edge_keys is read with the pass's own counters, and not zeroed with them
+    EmitCap ecap = {kRedEmit, first_cap(N, 2)};
+    Emitted e;
+    r = counted_emit(
+        h, "edge features", cnt, kRedMissing + 1, kRedBadEdges + 1, &ecap, 1,
+        [&] {
+            const int r = grow(h, h->ef_keys, sizeof(uint64_t) * (size_t)ecap.cap);
+            if (r != CTWS_OK) return r;
+            a.keys = (uint64_t*)h->ef_keys.p;
+            a.cap = ecap.cap;
+            if (data_dtype == CTWS_U8) k_ef_samples<uint8_t><<<g, 256, 0, h->stream>>>(a);
+            else k_ef_samples<float><<<g, 256, 0, h->stream>>>(a);
+            return CTWS_OK;
+        },
+        [&](const unsigned long long* w) {
+            if (!w[kRedBadEdges]) return CTWS_OK;
+            h->err = "edge features: " + std::to_string(w[kRedBadEdges]) +
                      " edges have an endpoint missing from the nodes or are not sorted and unique";
             return CTWS_EINVAL;
-        }
-        if (res[0] <= cap) break;
-        if (attempt == 1) {
-            h->err = "edge features: the sample count changed between two passes over the same block";
-            return CTWS_EHIP;
-        }
-        cap = res[0];
-    }
+        },
+        &e);
+    if (r != CTWS_OK) return r;
     record(h, 2);
-    const int64_t n = (int64_t)res[0];
-    if (n >= kMax) {
+    const int64_t n = (int64_t)e.w[kRedEmit];
+    if (n >= (1ll << 31)) {
         h->err = "edge features: 2^31 or more samples in one block";
         return CTWS_EUNSUPPORTED;
     }
-    if (n_missing) *n_missing = (int64_t)res[16];
+    if (n_missing) *n_missing = (int64_t)e.w[kRedMissing];
     const uint64_t* sorted = (const uint64_t*)h->ef_keys.p;
     if (n) {
         size_t tb = 0;
@@ -4227,13 +4208,12 @@ int edge_features_block(ctws_handle* h, const uint64_t* labels, const void* data
     k_ef_stats<<<(unsigned)((n_edges + 3) / 4), 256, 0, h->stream>>>(sorted, (uint32_t)n, (uint32_t)n_edges, dout);
     LAUNCHCHK();
     record(h, 4);
-    if (!dev) HIPCHK(hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    rag_time(h, "ef_edge_keys", 0, 1);
-    rag_time(h, "ef_samples", 1, 2);
-    rag_time(h, "ef_sort", 2, 3);
-    rag_time(h, "ef_stats", 3, 4);
-    add_timing(h, "ef_sample_passes", (float)(attempt + 1));
+    if ((r = out_end(h, out, dout, out_bytes, dev)) != CTWS_OK) return r;
+    stage_time(h, "ef_edge_keys", 0, 1);
+    stage_time(h, "ef_samples", 1, 2);
+    stage_time(h, "ef_sort", 2, 3);
+    stage_time(h, "ef_stats", 3, 4);
+    add_timing(h, "ef_sample_passes", (float)e.passes);
     add_timing(h, "ef_keys", (float)n);
     return CTWS_OK;
 }

@@ -134,6 +134,16 @@ class CtwsError(RuntimeError):
     pass
 
 
+def _dtype_name(dtype):
+    """'uint8', 'float32', ... of a numpy or a torch dtype."""
+    return str(dtype).replace('torch.', '')
+
+
+def _dtype_code(dtype):
+    """The library's dtype code of a numpy or a torch dtype."""
+    return dtype_code(np.dtype(_dtype_name(dtype)))
+
+
 class Handle:
     """One library handle = one GPU, one HIP stream, one device workspace."""
 
@@ -165,6 +175,17 @@ class Handle:
         if ret != CTWS_OK:
             msg = lib().ctws_last_error(self._h)
             raise CtwsError("%s failed (%i): %s" % (what, ret, msg.decode() if msg else ''))
+
+    def _call_sized(self, what, caps, call):
+        """call(*caps) -> (return code, a size per capacity, the outputs ...), with outputs that
+        call allocates (numpy or torch) at the given capacities.  It is called once more, at the
+        returned sizes, when the library says that a capacity was too small.  -> (sizes ...,
+        outputs ...) of the call that counts; raises as _check."""
+        res = call(*caps)
+        if res[0] == -1 and any(n > c for n, c in zip(res[1:], caps)):
+            res = call(*(max(n, 1) for n in res[1:1 + len(caps)]))
+        self._check(res[0], what)
+        return res[1:]
 
     def last_error(self):
         """Message of the last call (also set, with status CTWS_BLOCK_FAILED, for failed blocks)."""
@@ -622,10 +643,8 @@ class Handle:
         edge merge of MergeSubGraphs.  A call that hits the capacity is repeated once with the
         returned size."""
         n_pairs = int(np.asarray(pairs).size // 2)
-        ret, m, out, cnt = self.unique_pairs_u64_raw(pairs, weights, min(n_pairs, 4096))
-        if ret == -1 and m > len(cnt):
-            ret, m, out, cnt = self.unique_pairs_u64_raw(pairs, weights, m)
-        self._check(ret, 'ctws_unique_pairs_u64')
+        m, out, cnt = self._call_sized('ctws_unique_pairs_u64', (min(n_pairs, 4096),),
+                                       lambda cap: self.unique_pairs_u64_raw(pairs, weights, cap))
         return out[:m], cnt[:m]
 
     # first capacities of rag_block (nodes, edges): a 64 x 512 x 512 block of fragments has ~2,700
@@ -653,11 +672,8 @@ class Handle:
         (without 0 under ignore_label); edges = the sorted (min, max) id pairs of face-adjacent
         voxels with different ids (none with a 0 under ignore_label); counts = the voxel pairs per
         edge.  A call that hits a capacity is repeated once with the returned sizes."""
-        cn, ce = self.RAG_CAPS
-        ret, nn, ne, nodes, edges, counts = self.rag_block_raw(labels, ignore_label, cn, ce)
-        if ret == -1 and (nn > cn or ne > ce):
-            ret, nn, ne, nodes, edges, counts = self.rag_block_raw(labels, ignore_label, max(nn, 1), max(ne, 1))
-        self._check(ret, 'ctws_rag_block')
+        nn, ne, nodes, edges, counts = self._call_sized(
+            'ctws_rag_block', self.RAG_CAPS, lambda cn, ce: self.rag_block_raw(labels, ignore_label, cn, ce))
         return nodes[:nn], edges[:ne], counts[:ne]
 
     def rag_block_device(self, labels, ignore_label=True):
@@ -668,19 +684,17 @@ class Handle:
         assert labels.numel() > 0
         torch.cuda.current_stream(labels.device).synchronize()
         nn, ne = C.c_int64(0), C.c_int64(0)
-        cn, ce = self.RAG_CAPS
-        for _ in range(2):
+
+        def call(cn, ce):
             nodes = torch.empty(cn, dtype=torch.int64, device=labels.device)
             edges = torch.empty((ce, 2), dtype=torch.int64, device=labels.device)
             counts = torch.empty(ce, dtype=torch.int64, device=labels.device)
             ret = lib().ctws_rag_block_device(self._h, labels.data_ptr(), *labels.shape, int(bool(ignore_label)),
                                               nodes.data_ptr(), cn, C.byref(nn), edges.data_ptr(),
                                               counts.data_ptr(), ce, C.byref(ne))
-            if not (ret == -1 and (nn.value > cn or ne.value > ce)):
-                break
-            cn, ce = max(nn.value, 1), max(ne.value, 1)
-        self._check(ret, 'ctws_rag_block_device')
-        return nodes[:nn.value], edges[:ne.value], counts[:ne.value]
+            return ret, nn.value, ne.value, nodes, edges, counts
+        n, m, nodes, edges, counts = self._call_sized('ctws_rag_block_device', self.RAG_CAPS, call)
+        return nodes[:n], edges[:m], counts[:m]
 
     # ---- EdgeFeaturesWorkflow kernels ------------------------------------------------------
     def edge_features_block(self, labels, data, nodes, edges, ignore_label=True, core_shape=None):
@@ -735,11 +749,10 @@ class Handle:
             return out, 0
         torch.cuda.current_stream(labels.device).synchronize()
         miss = C.c_int64(0)
-        code = dtype_code(np.dtype('float32' if data.dtype == torch.float32 else 'uint8'))
-        self._check(lib().ctws_edge_features_block_device(self._h, labels.data_ptr(), data.data_ptr(), code,
-                                                          *labels.shape, *core, int(bool(ignore_label)),
-                                                          nodes.data_ptr(), nodes.numel(), edges.data_ptr(), m,
-                                                          out.data_ptr(), C.byref(miss)),
+        self._check(lib().ctws_edge_features_block_device(self._h, labels.data_ptr(), data.data_ptr(),
+                                                          _dtype_code(data.dtype), *labels.shape, *core,
+                                                          int(bool(ignore_label)), nodes.data_ptr(), nodes.numel(),
+                                                          edges.data_ptr(), m, out.data_ptr(), C.byref(miss)),
                     'ctws_edge_features_block_device')
         return out, int(miss.value)
 
@@ -786,11 +799,8 @@ class Handle:
             raise ValueError("label overlaps: fragments and labels are of one shape, not %s and %s"
                              % (nodes_vol.shape, labels_vol.shape))
         labels_vol = labels_vol.astype('uint64', copy=False)
-        cap = self.OVERLAP_CAP
-        ret, m, rows = self.label_overlaps_raw(nodes_vol, labels_vol, ignore_label, cap)
-        if ret == -1 and m > cap:
-            ret, m, rows = self.label_overlaps_raw(nodes_vol, labels_vol, ignore_label, m)
-        self._check(ret, 'ctws_label_overlaps')
+        m, rows = self._call_sized('ctws_label_overlaps', (self.OVERLAP_CAP,),
+                                   lambda cap: self.label_overlaps_raw(nodes_vol, labels_vol, ignore_label, cap))
         return rows[:m]
 
     def label_overlaps_device(self, nodes_vol, labels_vol, ignore_label=None):
@@ -803,16 +813,14 @@ class Handle:
         torch.cuda.current_stream(nodes_vol.device).synchronize()
         wi, il = self._ignore_args(ignore_label)
         n = C.c_int64(0)
-        cap = self.OVERLAP_CAP
-        for _ in range(2):
+
+        def call(cap):
             rows = torch.empty((cap, 3), dtype=torch.int64, device=nodes_vol.device)
             ret = lib().ctws_label_overlaps_device(self._h, nodes_vol.data_ptr(), labels_vol.data_ptr(),
                                                    nodes_vol.numel(), wi, il, rows.data_ptr(), cap, C.byref(n))
-            if not (ret == -1 and n.value > cap):
-                break
-            cap = n.value
-        self._check(ret, 'ctws_label_overlaps_device')
-        return rows[:n.value]
+            return ret, n.value, rows
+        m, rows = self._call_sized('ctws_label_overlaps_device', (self.OVERLAP_CAP,), call)
+        return rows[:m]
 
     # ---- MorphologyWorkflow kernels --------------------------------------------------------
     # first capacity of block_morphology in rows: a call that does not fit computes everything again
@@ -848,11 +856,8 @@ class Handle:
             raise TypeError("block morphology: the labels are uint64, not %s" % labels.dtype)
         if labels.ndim != 3 or not labels.size:
             raise ValueError("block morphology: the labels are a non-empty 3-D block, not %s" % (labels.shape,))
-        cap = self.MORPHOLOGY_CAP
-        ret, m, rows = self.block_morphology_raw(labels, begin, cap)
-        if ret == -1 and m > cap:
-            ret, m, rows = self.block_morphology_raw(labels, begin, m)
-        self._check(ret, 'ctws_block_morphology')
+        m, rows = self._call_sized('ctws_block_morphology', (self.MORPHOLOGY_CAP,),
+                                   lambda cap: self.block_morphology_raw(labels, begin, cap))
         return rows[:m]
 
     def block_morphology_device(self, labels, begin=(0, 0, 0)):
@@ -864,16 +869,14 @@ class Handle:
         torch.cuda.current_stream(labels.device).synchronize()
         b = self._begin_arg(begin)
         n = C.c_int64(0)
-        cap = self.MORPHOLOGY_CAP
-        for _ in range(2):
+
+        def call(cap):
             rows = torch.empty((cap, 11), dtype=torch.float64, device=labels.device)
             ret = lib().ctws_block_morphology_device(self._h, labels.data_ptr(), *labels.shape, b, rows.data_ptr(),
                                                      cap, C.byref(n))
-            if not (ret == -1 and n.value > cap):
-                break
-            cap = n.value
-        self._check(ret, 'ctws_block_morphology_device')
-        return rows[:n.value]
+            return ret, n.value, rows
+        m, rows = self._call_sized('ctws_block_morphology_device', (self.MORPHOLOGY_CAP,), call)
+        return rows[:m]
 
     # ---- RegionFeaturesWorkflow kernels ----------------------------------------------------
     # first capacity of region_features_block in rows: a call that does not fit computes everything again
@@ -900,9 +903,9 @@ class Handle:
 
     @classmethod
     def _region_features_check(cls, l_dtype, l_shape, d_dtype, d_shape):
-        if str(l_dtype).replace('torch.', '') != 'uint64':
+        if _dtype_name(l_dtype) != 'uint64':
             raise TypeError("region features: the labels are uint64, not %s" % (l_dtype,))
-        if str(d_dtype).replace('torch.', '') not in cls.REGION_FEATURES_DTYPES:
+        if _dtype_name(d_dtype) not in cls.REGION_FEATURES_DTYPES:
             raise TypeError("region features: the input map is uint8, uint16, float32 or float64, not %s"
                             % (d_dtype,))
         l_shape, d_shape = tuple(l_shape), tuple(d_shape)
@@ -918,11 +921,8 @@ class Handle:
         3-D shape -> rows (m, 3) float64 of [id, count, mean], a row per id of the block, sorted by
         id.  ignore_label not None: that id's row, if it occurs, is [id, 0, 0].  A call that hits
         the capacity is repeated once with the returned size."""
-        cap = self.REGION_FEATURES_CAP
-        ret, m, rows = self.region_features_block_raw(labels, data, ignore_label, cap)
-        if ret == -1 and m > cap:
-            ret, m, rows = self.region_features_block_raw(labels, data, ignore_label, m)
-        self._check(ret, 'ctws_region_features_block')
+        m, rows = self._call_sized('ctws_region_features_block', (self.REGION_FEATURES_CAP,),
+                                   lambda cap: self.region_features_block_raw(labels, data, ignore_label, cap))
         return rows[:m]
 
     def region_features_block_device(self, labels, data, ignore_label=0):
@@ -934,20 +934,18 @@ class Handle:
             assert t.is_cuda and t.is_contiguous()
         l_dtype = 'uint64' if labels.element_size() == 8 and not labels.is_floating_point() else labels.dtype
         self._region_features_check(l_dtype, labels.shape, data.dtype, data.shape)
-        code = dtype_code(np.dtype(str(data.dtype).replace('torch.', '')))
+        code = _dtype_code(data.dtype)
         torch.cuda.current_stream(labels.device).synchronize()
         wi, il = self._ignore_args(ignore_label)
         n = C.c_int64(0)
-        cap = self.REGION_FEATURES_CAP
-        for _ in range(2):
+
+        def call(cap):
             rows = torch.empty((cap, 3), dtype=torch.float64, device=labels.device)
             ret = lib().ctws_region_features_block_device(self._h, labels.data_ptr(), data.data_ptr(), code,
                                                           *labels.shape, wi, il, rows.data_ptr(), cap, C.byref(n))
-            if not (ret == -1 and n.value > cap):
-                break
-            cap = n.value
-        self._check(ret, 'ctws_region_features_block_device')
-        return rows[:n.value]
+            return ret, n.value, rows
+        m, rows = self._call_sized('ctws_region_features_block_device', (self.REGION_FEATURES_CAP,), call)
+        return rows[:m]
 
     # ---- DownscalingWorkflow kernel ---------------------------------------------------------
     DOWNSCALE_DTYPES = ('uint8', 'uint16', 'float32', 'float64')
@@ -956,7 +954,7 @@ class Handle:
     @classmethod
     def _downscale_check(cls, dtype, shape, factors, func):
         """The Python-side refusals of downscale_block: -> (factors, func code, output shape)."""
-        if str(dtype).replace('torch.', '') not in cls.DOWNSCALE_DTYPES:
+        if _dtype_name(dtype) not in cls.DOWNSCALE_DTYPES:
             raise TypeError("downscale: the block is uint8, uint16, float32 or float64, not %s" % (dtype,))
         shape = tuple(int(s) for s in shape)
         if len(shape) != 3 or 0 in shape:
@@ -1001,12 +999,11 @@ class Handle:
         import torch
         assert x.is_cuda and x.is_contiguous()
         fac, code, oshape = self._downscale_check(x.dtype, x.shape, factors, func)
-        dcode = dtype_code(np.dtype(str(x.dtype).replace('torch.', '')))
         torch.cuda.current_stream(x.device).synchronize()
         out = torch.empty(oshape, dtype=x.dtype, device=x.device)
         flag = C.c_int(-1)
-        ret = lib().ctws_downscale_block_device(self._h, x.data_ptr(), dcode, *x.shape, (C.c_int64 * 3)(*fac), code,
-                                                out.data_ptr(), *oshape, C.byref(flag))
+        ret = lib().ctws_downscale_block_device(self._h, x.data_ptr(), _dtype_code(x.dtype), *x.shape,
+                                                (C.c_int64 * 3)(*fac), code, out.data_ptr(), *oshape, C.byref(flag))
         self._check(ret, 'ctws_downscale_block_device')
         return out, bool(flag.value)
 

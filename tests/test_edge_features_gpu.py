@@ -68,6 +68,7 @@ def test_long_segment_beside_short_ones(gpu_handle):
     seg[0, 0, 0] = 3
     got, ref, counts = _check(gpu_handle, seg, _data(seg.shape, 1), True)
     assert counts.tolist() == [64 * 130, 3] and 2 * int(counts[0]) == 16640
+    assert gpu_handle.timings()['ef_sample_passes'] == 1.  # 16,646 keys in a first buffer of 33,280
     # one pair: every quantile lies between the only two samples
     seg[0, 0, 0] = 1
     seg[7, 63, 129] = 3

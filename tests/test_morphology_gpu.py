@@ -51,6 +51,7 @@ def test_small_shapes(gpu_handle, shape):
 def test_one_id_fills_the_block(gpu_handle):
     got = _check(gpu_handle, np.full((4, 8, 200), 9))  # runs of full length
     assert got.tolist() == [[9, 6400, 1.5, 3.5, 99.5, 0, 0, 0, 3, 7, 199]]
+    assert gpu_handle.timings()['morph_run_passes'] == 1.  # a run per row, or per word, fits 1,600
 
 
 @pytest.mark.parametrize('shape', [(1, 2, 384), (3, 4, 70)])
@@ -60,6 +61,8 @@ def test_every_voxel_distinct(gpu_handle, shape):
     lab = np.random.RandomState(1).permutation(n).reshape(shape)
     got = _check(gpu_handle, lab)
     assert len(got) == n and (got[:, 1] == 1).all()
+    if n > 256:  # more runs than the first buffer of max(64, n / 4) holds
+        assert gpu_handle.timings()['morph_run_passes'] == 2.
     np.testing.assert_array_equal(got[:, 2:5], got[:, 5:8])
 
 

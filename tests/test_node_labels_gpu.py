@@ -64,6 +64,7 @@ def test_constant(gpu_handle):
     nodes = np.full((4, 8, 64), 3, np.uint64)
     labels = np.full((4, 8, 64), 11, np.uint64)
     assert _check(gpu_handle, nodes, labels).tolist() == [[3, 11, 2048]]
+    assert gpu_handle.timings()['ov_pair_passes'] == 1.  # 32 runs in a first buffer of 512
 
 
 def test_every_voxel_distinct(gpu_handle):
@@ -76,6 +77,7 @@ def test_every_voxel_distinct(gpu_handle):
     labels = rng.randint(0, 3, size=nodes.shape).astype(np.uint64)
     rows = _check(gpu_handle, nodes, labels)
     assert len(rows) == nodes.size and (rows[:, 2] == 1).all()
+    assert gpu_handle.timings()['ov_pair_passes'] == 2.
 
 
 def test_one_pair_large(gpu_handle):

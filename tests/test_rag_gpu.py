@@ -44,6 +44,7 @@ def test_every_pair_its_own_edge(gpu_handle, ignore_label):
     seg = (np.arange(5 * 6 * 67).reshape(5, 6, 67) + 1).astype(np.uint64)
     nodes, edges, counts = _check(gpu_handle, seg, ignore_label)
     assert len(nodes) == seg.size and len(edges) == 5263 and (counts == 1).all()
+    assert gpu_handle.timings()['rag_pair_passes'] == 2.
 
 
 def _far_face_cases():
@@ -78,6 +79,7 @@ def test_degenerate_blocks(gpu_handle):
     for ignore_label in (False, True):
         nodes, edges, counts = _check(gpu_handle, const, ignore_label)
         assert nodes.tolist() == [7] and edges.shape == (0, 2) and counts.shape == (0,)
+        assert gpu_handle.timings()['rag_pair_passes'] == 1.  # no pair and one node id: both fit
     zero = np.zeros((3, 5, 70), np.uint64)
     nodes, edges, counts = _check(gpu_handle, zero, True)
     assert nodes.shape == (0,) and edges.shape == (0, 2) and counts.shape == (0,)
