@@ -384,6 +384,33 @@ __global__ void k_regfeat_rows(const uint64_t*, const uint64_t*, const double*, 
                                const uint64_t*, uint32_t, const uint64_t*, const double*, double*);
 hipError_t u32_exclusive_sum(void* tmp, size_t& bytes, const uint32_t* in, uint32_t* out, int64_t n,
                              hipStream_t stream);
+// k_regcenter.hip (RegionCentersWorkflow: per object the first voxel of its box with the largest
+// exact squared distance to the box's background)
+constexpr uint32_t kRcInf = 0xFFFFFFFFu;  // a line without background (every finite value is below 2^31)
+// k_rc_small: two uint32 arrays of the box in LDS, 80,000 B, so that two workgroups of 512 threads
+// with their reduction words share a CU's 160 KiB (163,840 B)
+constexpr int kRcSmallVox = 10000;
+constexpr int kRcSmallThreads = 512;
+// k_rc_col: the staged tile (line x W) in words, 32,640 B: five workgroups per CU with their
+// reduction words
+constexpr int kRcColWords = 8160;
+struct RcObj {
+    uint64_t id;          // the object's voxels: label == id, on all 64 bits
+    int64_t off;          // of the box's first voxel in the label buffer, in elements
+    int64_t pz, py;       // the z and y pitches in elements (x is contiguous)
+    uint32_t nz, ny, nx;  // the box: nz * ny * nx < 2^31
+    uint32_t wy, wz;      // k_rc_col's tile width of the y and z pass (0: the line does not fit the LDS)
+    uint64_t sbase;       // larger boxes: of the box in the two scratch arrays, in elements
+};
+struct RcRes {
+    uint32_t z2, y2, x2;  // the squared resolutions
+};
+__global__ void k_rc_small(const uint64_t*, const RcObj*, const uint32_t*, RcRes, unsigned long long*);
+__global__ void k_rc_rows(const uint64_t*, const RcObj*, const uint32_t*, RcRes, uint32_t*);
+template <bool STAGE>
+__global__ void k_rc_col(const RcObj*, const uint32_t*, int, uint32_t, int, const uint32_t*, uint32_t*,
+                         unsigned long long*);
+__global__ void k_rc_finish(const RcObj*, uint32_t, const unsigned long long*, long long*, uint8_t*);
 // k_downscale.hip (DownscalingWorkflow: mean / max / min over fz x fy x fx cells, zero-padded ends)
 constexpr int kDsMean = 0, kDsMax = 1, kDsMin = 2;
 struct DownscaleArgs {

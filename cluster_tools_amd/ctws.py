@@ -84,6 +84,9 @@ def lib():
                 getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64,
                                            C.POINTER(C.c_int64), C.c_int, C.c_void_p, C.c_int64, C.c_int64,
                                            C.c_int64, C.POINTER(C.c_int)]
+            for fn in ('ctws_region_centers', 'ctws_region_centers_device'):
+                getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_void_p]
             for fn in ('ctws_edge_features_block', 'ctws_edge_features_block_device'):
                 getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_int64] * 6 + [
                     C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]
@@ -115,7 +118,7 @@ EXPORTED_SYMBOLS = ('ctws_abi_version', 'ctws_open', 'ctws_close', 'ctws_last_er
                     'ctws_edge_features_block', 'ctws_edge_features_block_device', 'ctws_label_overlaps',
                     'ctws_label_overlaps_device', 'ctws_block_morphology', 'ctws_block_morphology_device',
                     'ctws_region_features_block', 'ctws_region_features_block_device', 'ctws_downscale_block',
-                    'ctws_downscale_block_device')
+                    'ctws_downscale_block_device', 'ctws_region_centers', 'ctws_region_centers_device')
 
 
 def ufd_find(n_labels, pairs):
@@ -946,6 +949,115 @@ class Handle:
             return ret, n.value, rows
         m, rows = self._call_sized('ctws_region_features_block_device', (self.REGION_FEATURES_CAP,), call)
         return rows[:m]
+
+    # ---- RegionCentersWorkflow kernels -------------------------------------------------------
+    # boxes of at most this many voxels run one workgroup each with the transform in LDS
+    # (ctws_kernels.h kRcSmallVox); timings() reports rc_small_objects / rc_large_objects
+    REGION_CENTERS_SMALL_VOXELS = 10000
+
+    @staticmethod
+    def _resolution_arg(resolution):
+        res = [float(r) for r in resolution]
+        if len(res) != 3:
+            raise ValueError("region centers: the resolution has three entries, not %s" % (resolution,))
+        return (C.c_double * 3)(*res)
+
+    def _region_centers_call(self, fn, labels_ptr, n_labels, ids, offsets, shapes, pitches, resolution, out):
+        """One ctws_region_centers / _device call over object tables (ids (k,), offsets (k,), shapes
+        (k, 3), pitches (k, 2)); out(k) -> (centers, found, their two pointers)."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint64).reshape(-1)
+        k = len(ids)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        shapes = np.ascontiguousarray(shapes, dtype=np.int64).reshape(-1, 3)
+        pitches = np.ascontiguousarray(pitches, dtype=np.int64).reshape(-1, 2)
+        if not (len(offsets) == len(shapes) == len(pitches) == k):
+            raise ValueError("region centers: %i ids, %i offsets, %i shapes, %i pitches"
+                             % (k, len(offsets), len(shapes), len(pitches)))
+        centers, found, pc, pf = out(k)
+        ret = getattr(lib(), fn)(self._h, labels_ptr, int(n_labels), k, ids.ctypes.data, offsets.ctypes.data,
+                                 shapes.ctypes.data, pitches.ctypes.data, self._resolution_arg(resolution), pc, pf)
+        self._check(ret, fn)
+        return centers, found
+
+    @staticmethod
+    def _region_centers_host_out(k):
+        centers = np.zeros((k, 3), dtype=np.int64)
+        found = np.zeros(k, dtype=np.uint8)
+        return centers, found, centers.ctypes.data, found.ctypes.data
+
+    @staticmethod
+    def _box_tables(shape, boxes):
+        """(k, 6) boxes [begin_z, begin_y, begin_x, end_z, end_y, end_x) inside a C-order volume of
+        `shape` -> offsets, shapes, pitches of the call.  A box with end <= begin on an axis is
+        empty; a box that leaves the volume is refused."""
+        boxes = np.asarray(boxes, dtype=np.int64).reshape(-1, 6)
+        Z, Y, X = (int(s) for s in shape)
+        begin, end = boxes[:, :3], boxes[:, 3:]
+        if len(boxes) and ((begin < 0).any() or (end > np.array([Z, Y, X])).any()):
+            raise ValueError("region centers: a box leaves the volume of shape %s" % (tuple(shape),))
+        shapes = np.maximum(end - begin, 0)
+        offsets = (begin[:, 0] * Y + begin[:, 1]) * X + begin[:, 2]
+        offsets = np.where((shapes == 0).any(axis=1), 0, offsets)
+        pitches = np.tile(np.array([Y * X, X], dtype=np.int64), (len(boxes), 1))
+        return offsets, shapes, pitches
+
+    def region_centers(self, crops, ids, resolution=(1, 1, 1)):
+        """The region centres of k objects given as crops (include/ctws.h, ctws_region_centers):
+        crops is a list of 3-D uint64 arrays, one per object, packed into one buffer; ids (k,) the
+        objects' ids.  -> (centers int64 (k, 3): per object the local (z, y, x) of the first voxel
+        in C order with the largest exact squared distance to the crop's voxels of another label,
+        scaled by the integer `resolution`; found bool (k,): False for an empty crop and for a crop
+        without a voxel of its id, whose centre is (0, 0, 0))."""
+        crops = [np.asarray(c) for c in crops]
+        for c in crops:
+            if c.dtype != np.dtype('uint64'):
+                raise TypeError("region centers: the labels are uint64, not %s" % c.dtype)
+            if c.ndim != 3:
+                raise ValueError("region centers: a crop is 3-D, not %s" % (c.shape,))
+        shapes = np.array([c.shape for c in crops], dtype=np.int64).reshape(-1, 3)
+        sizes = shapes.prod(axis=1)
+        offsets = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64) if len(crops) else np.zeros(0, np.int64)
+        pitches = np.stack([shapes[:, 1] * shapes[:, 2], shapes[:, 2]], axis=1)
+        buf = np.empty(int(sizes.sum()), dtype=np.uint64)
+        for c, o, n in zip(crops, offsets, sizes):
+            buf[o:o + n] = c.reshape(-1)
+        centers, found = self._region_centers_call('ctws_region_centers', buf.ctypes.data if buf.size else None,
+                                                   buf.size, ids, offsets, shapes, pitches, resolution,
+                                                   self._region_centers_host_out)
+        return centers, found.astype(bool)
+
+    def region_centers_boxes(self, labels, ids, boxes, resolution=(1, 1, 1)):
+        """region_centers for (k, 6) boxes [begin, end) inside one 3-D uint64 array: the boxes are
+        read in place at the array's pitches."""
+        labels = np.asarray(labels)
+        if labels.dtype != np.dtype('uint64'):
+            raise TypeError("region centers: the labels are uint64, not %s" % labels.dtype)
+        if labels.ndim != 3:
+            raise ValueError("region centers: the labels are a 3-D array, not %s" % (labels.shape,))
+        labels = np.ascontiguousarray(labels)
+        offsets, shapes, pitches = self._box_tables(labels.shape, boxes)
+        centers, found = self._region_centers_call('ctws_region_centers', labels.ctypes.data if labels.size else None,
+                                                   labels.size, ids, offsets, shapes, pitches, resolution,
+                                                   self._region_centers_host_out)
+        return centers, found.astype(bool)
+
+    def region_centers_boxes_device(self, labels, ids, boxes, resolution=(1, 1, 1)):
+        """region_centers_boxes on a uint64 / int64 torch tensor on this GPU; centers (int64) and
+        found (bool) come back as tensors on the same device."""
+        import torch
+        assert labels.is_cuda and labels.is_contiguous() and labels.element_size() == 8 and labels.dim() == 3
+        assert not labels.is_floating_point()
+        torch.cuda.current_stream(labels.device).synchronize()
+        offsets, shapes, pitches = self._box_tables(labels.shape, boxes)
+
+        def out(k):
+            centers = torch.zeros((k, 3), dtype=torch.int64, device=labels.device)
+            found = torch.zeros(k, dtype=torch.uint8, device=labels.device)
+            return centers, found, centers.data_ptr(), found.data_ptr()
+        centers, found = self._region_centers_call('ctws_region_centers_device',
+                                                   labels.data_ptr() if labels.numel() else None, labels.numel(),
+                                                   ids, offsets, shapes, pitches, resolution, out)
+        return centers, found.bool()
 
     # ---- DownscalingWorkflow kernel ---------------------------------------------------------
     DOWNSCALE_DTYPES = ('uint8', 'uint16', 'float32', 'float64')

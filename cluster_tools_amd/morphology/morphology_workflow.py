@@ -2,12 +2,18 @@
 (cluster_tools/morphology/morphology_workflow.py:11-56; parameters and config keys unchanged): the
 (maxId + 1, 11) float64 table [id, size, com_z, com_y, com_x, min_z, min_y, min_x, max_z, max_y,
 max_x] of a label volume.  The block tables go to `morphology_<prefix>` in the output file.
-RegionCentersWorkflow (:59-94) is not built."""
+
+RegionCentersWorkflow: MorphologyWorkflow -> RegionCenters (:59-94; parameters and config keys
+unchanged): the (maxId + 1, 3) float32 table of the voxel of every object that is farthest from its
+border.  The morphology table goes to `<tmp_folder>/region_centers.n5:morphology`."""
+import os
+
 from cluster_tools_amd import luigi_compat as luigi
 from cluster_tools_amd.cluster_tasks import WorkflowBase
 from cluster_tools_amd.utils import volume_utils as vu
 from cluster_tools_amd.morphology import block_morphology as block_tasks
 from cluster_tools_amd.morphology import merge_morphology as merge_tasks
+from cluster_tools_amd.morphology import region_centers as center_tasks
 
 
 class MorphologyWorkflow(WorkflowBase):
@@ -43,4 +49,33 @@ class MorphologyWorkflow(WorkflowBase):
         configs = WorkflowBase.get_config()
         configs.update({'block_morphology': block_tasks.BlockMorphologyLocal.default_task_config(),
                         'merge_morphology': merge_tasks.MergeMorphologyLocal.default_task_config()})
+        return configs
+
+
+class RegionCentersWorkflow(WorkflowBase):
+    input_path = luigi.Parameter()
+    input_key = luigi.Parameter()
+    output_path = luigi.Parameter()
+    output_key = luigi.Parameter()
+    ignore_label = luigi.Parameter(default=None)
+    resolution = luigi.ListParameter(default=[1, 1, 1])
+
+    def requires(self):
+        tmp_path = os.path.join(self.tmp_folder, 'region_centers.n5')
+        tmp_key = 'morphology'
+        dep = MorphologyWorkflow(tmp_folder=self.tmp_folder, max_jobs=self.max_jobs, config_dir=self.config_dir,
+                                 target=self.target, input_path=self.input_path, input_key=self.input_key,
+                                 output_path=tmp_path, output_key=tmp_key, dependency=self.dependency,
+                                 prefix='region-centers')
+        center_task = getattr(center_tasks, self._get_task_name('RegionCenters'))
+        return center_task(tmp_folder=self.tmp_folder, config_dir=self.config_dir, max_jobs=self.max_jobs,
+                           dependency=dep, input_path=self.input_path, input_key=self.input_key,
+                           morphology_path=tmp_path, morphology_key=tmp_key, output_path=self.output_path,
+                           output_key=self.output_key, ignore_label=self.ignore_label, resolution=self.resolution)
+
+    @staticmethod
+    def get_config():
+        configs = WorkflowBase.get_config()
+        configs.update({'region_centers': center_tasks.RegionCentersLocal.default_task_config(),
+                        **MorphologyWorkflow.get_config()})
         return configs

@@ -1,0 +1,204 @@
+#! /usr/bin/env python
+"""RegionCenters: for every id the voxel inside the object that is farthest from its border, on the
+GPU (cluster_tools/morphology/region_centers.py:25-185; task surface, job config keys, id_chunks =
+2000, output dataset and log lines unchanged).  The job replaces the reference's serial
+`distance_transform_edt` + `np.argmax` per id (:106-133) by `Handle.region_centers`: one library
+handle per job, the morphology table read once, and per id chunk the objects' crops read ahead on a
+thread, gathered into calls and their centres plus box begins written as the reference writes them.
+
+What is kept from the reference, restated in DESIGN.md section 3.10: the box of an id is
+[min, max) of its morphology row -- the table's maxima are inclusive, so the last plane of every
+axis is left out, and an object of extent 1 on some axis keeps its zero row; `ignore_label ==
+label_id` skips an id; an object without a voxel in its box keeps its zero row.
+
+Only integer resolutions are computed (given as int, or as float with an integral value): with
+them the squared distances are exact integers and the argmax equals scipy's.  Any other resolution
+raises NotImplementedError before a job starts.
+
+A call takes crops of at most CALL_BYTES of labels (a crop above that is a call of its own).  Many
+fragments' crops are a few thousand voxels, and a library call costs tens of microseconds whatever
+it holds, so a call should hold many; but its crops are packed on the host, staged in HBM and, for
+the larger boxes, transformed in 8 bytes per voxel of scratch, so the budget bounds the host and
+device memory of a job at about three times its value, and while one call runs the next one's
+crops are being read.  256 MiB holds the 2000 ids of a chunk in one call for typical fragments and
+is small beside a GPU's memory."""
+import json
+import os
+import sys
+from concurrent import futures
+
+import numpy as np
+
+from cluster_tools_amd import luigi_compat as luigi
+import cluster_tools_amd.utils.volume_utils as vu
+import cluster_tools_amd.utils.function_utils as fu
+from cluster_tools_amd.utils.blocking import Blocking
+from cluster_tools_amd.cluster_tasks import SlurmTask, LocalTask, LSFTask
+
+CALL_BYTES = 256 << 20
+MAX_RESOLUTION = 1 << 10
+D2_LIMIT = 1 << 31     # sum_a (resolution_a extent_a)^2 of a box stays below: the transform is 32-bit
+VOXEL_LIMIT = 1 << 31  # voxels of a box
+
+
+def integer_resolution(resolution):
+    """The resolution as three ints, or NotImplementedError."""
+    res = [float(r) for r in resolution]
+    if len(res) != 3:
+        raise ValueError("region_centers: resolution has three entries, not %s" % (list(resolution),))
+    if any(not (r > 0) for r in res):
+        raise ValueError("region_centers: resolution %s is not positive" % (list(resolution),))
+    if any(r != int(r) or r > MAX_RESOLUTION for r in res):
+        raise NotImplementedError(
+            "region_centers: resolution %s is not three integers of at most %i.  Only integer resolutions are "
+            "computed: their squared distances are exact, so the centre equals the reference's; with other values "
+            "scipy's float64 roundings decide ties.  The centre does not change when all three values are scaled "
+            "by a common factor: give [0.04, 0.004, 0.004] as [10, 1, 1]" % (list(resolution), MAX_RESOLUTION))
+    return [int(r) for r in res]
+
+
+class RegionCentersBase(luigi.Task):
+    task_name = 'region_centers'
+    src_file = os.path.abspath(__file__)
+    allow_retry = False
+
+    input_path = luigi.Parameter()
+    input_key = luigi.Parameter()
+    morphology_path = luigi.Parameter()
+    morphology_key = luigi.Parameter()
+    output_path = luigi.Parameter()
+    output_key = luigi.Parameter()
+    ignore_label = luigi.Parameter(default=None)
+    resolution = luigi.ListParameter(default=[1, 1, 1])
+    dependency = luigi.TaskParameter()
+
+    def requires(self):
+        return self.dependency
+
+    def run_impl(self):
+        shebang = self.global_config_values()[0]
+        self.init(shebang)
+        integer_resolution(self.resolution)  # refused here, before any job starts
+        config = self.get_task_config()
+        number_of_labels = int(vu.file_reader(self.input_path, 'r')[self.input_key].attrs['maxId']) + 1
+        id_chunks = 2000
+        block_list = vu.blocks_in_volume([number_of_labels], [id_chunks])
+        with vu.file_reader(self.output_path) as f:
+            f.require_dataset(self.output_key, shape=(number_of_labels, 3), chunks=(id_chunks, 3), dtype='float32',
+                              compression='gzip')
+        config.update({'input_path': self.input_path, 'input_key': self.input_key,
+                       'morphology_path': self.morphology_path, 'morphology_key': self.morphology_key,
+                       'output_path': self.output_path, 'output_key': self.output_key,
+                       'ignore_label': self.ignore_label, 'resolution': list(self.resolution),
+                       'id_chunks': id_chunks})
+        n_jobs = min(self.max_jobs, len(block_list))
+        self.prepare_jobs(n_jobs, block_list, config)
+        self.submit_jobs(n_jobs)
+        self.wait_for_jobs()
+        self.check_jobs(n_jobs)
+
+
+class RegionCentersLocal(RegionCentersBase, LocalTask):
+    pass
+
+
+class RegionCentersSlurm(RegionCentersBase, SlurmTask):
+    pass
+
+
+class RegionCentersLSF(RegionCentersBase, LSFTask):
+    pass
+
+
+#
+# Implementation
+#
+
+def _device():
+    return int(os.environ.get('CTWS_DEVICE', os.environ.get('LOCAL_RANK', '0')))
+
+
+def plan_calls(bb_start, bb_stop, label_begin, label_end, ignore_label, resolution, call_bytes=CALL_BYTES):
+    """The ids of [label_begin, label_end) that have a non-empty box [bb_start, bb_stop), dealt to
+    calls of at most call_bytes of labels: a list of lists of (label_id, begin, end).  An id whose
+    box breaks a limit of the kernels raises."""
+    calls, cur, cur_bytes = [], [], 0
+    for label_id in range(label_begin, label_end):
+        if ignore_label == label_id or label_id >= len(bb_start):
+            continue
+        begin = [int(b) for b in bb_start[label_id]]
+        end = [int(e) for e in bb_stop[label_id]]
+        ext = [e - b for b, e in zip(begin, end)]
+        if min(ext) <= 0:
+            continue
+        if sum((r * n) ** 2 for r, n in zip(resolution, ext)) >= D2_LIMIT:
+            raise RuntimeError("region_centers: id %i has a box of %s voxels; at resolution %s its squared distances "
+                               "reach 2^31, above the 32-bit transform's limit sum((resolution * extent)^2) < 2^31"
+                               % (label_id, ext, list(resolution)))
+        n_vox = ext[0] * ext[1] * ext[2]
+        if n_vox >= VOXEL_LIMIT:
+            raise RuntimeError("region_centers: id %i has a box of %s = %i voxels, above the limit of 2^31 - 1 voxels "
+                               "per box" % (label_id, ext, n_vox))
+        if cur and cur_bytes + 8 * n_vox > call_bytes:
+            calls.append(cur)
+            cur, cur_bytes = [], 0
+        cur.append((label_id, begin, end))
+        cur_bytes += 8 * n_vox
+    if cur:
+        calls.append(cur)
+    return calls
+
+
+def region_centers_for_label_range(h, io, ds_in, ds_out, bb_start, bb_stop, label_begin, label_end, ignore_label,
+                                   resolution):
+    centers = np.zeros((label_end - label_begin, 3), dtype='float32')
+    calls = plan_calls(bb_start, bb_stop, label_begin, label_end, ignore_label, resolution)
+
+    def read(call):
+        return [np.ascontiguousarray(ds_in[tuple(slice(b, e) for b, e in zip(begin, end))], dtype='uint64')
+                for _, begin, end in call]
+
+    nxt = io.submit(read, calls[0]) if calls else None
+    for k, call in enumerate(calls):
+        crops = nxt.result()
+        nxt = io.submit(read, calls[k + 1]) if k + 1 < len(calls) else None
+        local, found = h.region_centers(crops, [label_id for label_id, _, _ in call], resolution)
+        for (label_id, begin, _), c, ok in zip(call, local, found):
+            if ok:  # (an object without a voxel in its box keeps its zero row)
+                centers[label_id - label_begin] = c + np.array(begin, dtype='int64')
+    ds_out[label_begin:label_end] = centers
+
+
+def region_centers(job_id, config_path):
+    from cluster_tools_amd import ctws
+    fu.log("start processing job %i" % job_id)
+    fu.log("reading config from %s" % config_path)
+    with open(config_path) as f:
+        config = json.load(f)
+    input_path, input_key = config['input_path'], config['input_key']
+    ignore_label = config['ignore_label']
+    resolution = integer_resolution(config['resolution'])
+    block_list = config['block_list']
+    id_chunks = config['id_chunks']
+    number_of_labels = int(vu.file_reader(input_path, 'r')[input_key].attrs['maxId']) + 1
+    blocking = Blocking([0], [number_of_labels], [id_chunks])
+    with vu.file_reader(config['morphology_path'], 'r') as f:
+        morphology = f[config['morphology_key']][:]
+    bb_start = morphology[:, 5:8].astype('uint64')
+    bb_stop = morphology[:, 8:11].astype('uint64')
+    with vu.file_reader(input_path, 'r') as f_in, vu.file_reader(config['output_path']) as f_out, \
+            ctws.Handle(_device()) as h, futures.ThreadPoolExecutor(1) as io:
+        ds_in = f_in[input_key]
+        ds_out = f_out[config['output_key']]
+        for block_id in block_list:
+            block = blocking.getBlock(block_id)
+            region_centers_for_label_range(h, io, ds_in, ds_out, bb_start, bb_stop, int(block.begin[0]),
+                                           int(block.end[0]), ignore_label, resolution)
+    fu.log_job_success(job_id)
+
+
+if __name__ == '__main__':
+    path = sys.argv[1]
+    assert os.path.exists(path), path
+    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
+    region_centers(job_id, path)

@@ -426,6 +426,48 @@ int ctws_downscale_block_device(ctws_handle* h, const void* input, int dtype, in
                                 int* any_nonzero);
 
 /*
+ * RegionCentersWorkflow (morphology/morphology_workflow.py:59-112), RegionCenters: per object the
+ * voxel of its box that is farthest from the box's background (region_centers.py:106-133,
+ * `np.argmax(distance_transform_edt(labels[box] == id, sampling=resolution))`, restated: DESIGN.md
+ * section 3.10).
+ *
+ * ctws_region_centers / _device: labels is one buffer of n_labels uint64 ids that holds the boxes
+ *   of k objects.  Object i is ids[i], offsets[i] (of the box's first voxel, in elements),
+ *   shapes[3 i ..] = (nz, ny, nx) and pitches[2 i ..] = (z pitch, y pitch) in elements, x
+ *   contiguous: packed crops one after another (pitches (ny nx, nx)) and boxes inside one resident
+ *   volume (the volume's pitches) are the same call.  ids, offsets, shapes, pitches and resolution
+ *   are always host pointers.
+ *     d2      of a voxel p with label == ids[i] (all 64 bits compare): the minimum over the box's
+ *             voxels b with another label of sum_a (resolution[a] (p_a - b_a))^2, an exact integer;
+ *             0 for the other voxels.  Only voxels inside the box count as background.
+ *     centers k x 3 int64, C order: the local (z, y, x) of the first voxel in C order of the box with
+ *             the largest d2.  A box without background gives its last voxel, shape - 1 (scipy
+ *             1.15 treats such a box as if one background voxel sat at local (-1, 0, 0)).
+ *     found   k x uint8: 0 when the box is empty (an extent of 0) or holds no voxel of the id; the
+ *             centre is then (0, 0, 0).
+ *   Limits, CTWS_EUNSUPPORTED otherwise and never a wrong centre: every resolution an integer in
+ *   1 .. 2^10 (given as double; with a non-integer value the reference's float64 roundings decide
+ *   ties, which is not restated; the centre does not change when all three values are scaled by a
+ *   common factor); sum_a (resolution[a] shape[a])^2 < 2^31 per box (d2 is 32-bit); fewer than 2^31
+ *   voxels per box; fewer than 2^31 objects.  CTWS_EINVAL for a box that does not lie inside the
+ *   buffer, rows that overlap (y pitch < nx, z pitch < (ny - 1) y pitch + nx) or a negative value;
+ *   nothing is launched then.
+ *   Boxes of at most 10000 voxels run one workgroup each, all in one launch, with the transform in
+ *   LDS; larger boxes run separable passes through scratch memory of the handle (8 bytes per box
+ *   voxel, in groups of at most 2^28 voxels).  ctws_last_timings reports rc_small_objects and
+ *   rc_large_objects.  The maximum is taken over integer keys (d2, first index): the result
+ *   depends on the inputs alone, repeated calls agree byte for byte.  Host pointers are staged
+ *   through HBM; _device takes device pointers on the handle's GPU for labels, centers and found.
+ */
+int ctws_region_centers(ctws_handle* h, const uint64_t* labels, int64_t n_labels, int64_t k, const uint64_t* ids,
+                        const int64_t* offsets, const int64_t* shapes, const int64_t* pitches,
+                        const double resolution[3], int64_t* centers, uint8_t* found);
+int ctws_region_centers_device(ctws_handle* h, const uint64_t* labels, int64_t n_labels, int64_t k,
+                               const uint64_t* ids, const int64_t* offsets, const int64_t* shapes,
+                               const int64_t* pitches, const double resolution[3], int64_t* centers,
+                               uint8_t* found);
+
+/*
  * EdgeFeaturesWorkflow (features/features_workflow.py:14-66), BlockEdgeFeatures: the boundary-map
  * statistics of the edges of one block (block_edge_features.py:113-132,
  * `ndist.extractBlockFeaturesFromBoundaryMaps_*`, restated: DESIGN.md section 3.5).
