@@ -474,4 +474,30 @@ __global__ void k_tc_raw_members(const T*, int64_t, int, double, float*);
 __global__ void k_tc_normalize(float*, int64_t, const uint32_t*);
 __global__ void k_tc_gauss(const float*, float*, int, int, int, int, const double*, int);
 
+// k_imgfilter.hip (ImageFilter: Gaussian smoothing, gradient magnitude, Laplacian of Gaussian)
+constexpr int kIfMaxR = 48;    // largest tap radius: 2 inputs x (kIfColTL + 2 kIfMaxR) x kIfColW floats = 64 KiB of LDS
+constexpr int kIfColTL = 32;   // column pass: outputs along the axis per tile
+constexpr int kIfColW = 64;    // column pass: x positions per tile (a wave's lanes)
+constexpr int kIfRowW = 256;   // row pass: outputs per row segment (4 per lane)
+constexpr int kIfSmooth = 0, kIfGradMag = 1, kIfLaplace = 2;
+struct IfArgs {
+    const void* in[3];    // column pass: NIN arrays of the kernel's type T; row pass: NIN float arrays
+    float* out[3];        // column pass: NOUT arrays; row pass: out[0]
+    int tap[3], rad[3];   // first tap (offset -rad) in taps and radius, per output (column) or per input (row)
+    const double* taps;
+    const uint32_t* mm;   // normalize: ordered-float bits of the block's min and max (k_if_minmax)
+    int normalize;        // 1: the pass reads (float(x) - min) / fl(max - min), vu.normalize on the fly
+    int nz, ny, nx;       // nz * ny * nx < 2^31
+    int axis;             // column pass: 0 (z) or 1 (y)
+    int rmax;             // max over rad: the tile's halo (every line holds at least rmax + 1 voxels)
+    int combine;          // row pass: kIfSmooth the one result, kIfGradMag sqrt of the squares' sum, kIfLaplace the sum
+};
+template <class T>
+__global__ void k_if_minmax(const T*, int64_t, uint32_t*);
+// outputs of a column pass: NIN = 1: all of input 0; NIN = 2: output 0 of input 0, outputs 1, 2 of input 1
+template <class T, int NIN, int NOUT>
+__global__ void k_if_col(IfArgs);
+template <int NIN>
+__global__ void k_if_row(IfArgs);
+
 }  // namespace ctws

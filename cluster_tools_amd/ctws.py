@@ -84,6 +84,10 @@ def lib():
                 getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64,
                                            C.POINTER(C.c_int64), C.c_int, C.c_void_p, C.c_int64, C.c_int64,
                                            C.c_int64, C.POINTER(C.c_int)]
+            L.ctws_filter_taps.argtypes = [C.c_double, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
+            for fn in ('ctws_image_filter', 'ctws_image_filter_device'):
+                getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64,
+                                           C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_void_p]
             for fn in ('ctws_region_centers', 'ctws_region_centers_device'):
                 getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_void_p]
@@ -118,7 +122,8 @@ EXPORTED_SYMBOLS = ('ctws_abi_version', 'ctws_open', 'ctws_close', 'ctws_last_er
                     'ctws_edge_features_block', 'ctws_edge_features_block_device', 'ctws_label_overlaps',
                     'ctws_label_overlaps_device', 'ctws_block_morphology', 'ctws_block_morphology_device',
                     'ctws_region_features_block', 'ctws_region_features_block_device', 'ctws_downscale_block',
-                    'ctws_downscale_block_device', 'ctws_region_centers', 'ctws_region_centers_device')
+                    'ctws_downscale_block_device', 'ctws_region_centers', 'ctws_region_centers_device',
+                    'ctws_filter_taps', 'ctws_image_filter', 'ctws_image_filter_device')
 
 
 def ufd_find(n_labels, pairs):
@@ -135,6 +140,49 @@ def ufd_find(n_labels, pairs):
 
 class CtwsError(RuntimeError):
     pass
+
+
+# ImageFilter: the filters the library computes (one float32 value per voxel) and vigra's
+# multi-channel ones, which the reference's 3-D float32 output dataset cannot hold either
+IMAGE_FILTERS = {'gaussianSmoothing': 0, 'gaussianGradientMagnitude': 1, 'laplacianOfGaussian': 2}
+MULTI_CHANNEL_FILTERS = ('gaussianGradient', 'hessianOfGaussian', 'hessianOfGaussianEigenvalues',
+                         'structureTensor', 'structureTensorEigenvalues')
+
+
+def filter_taps(sigma, order):
+    """The 2 r + 1 double taps (offsets -r .. r) of the Gaussian (order 0) or its first or second
+    derivative as the library's filters use them (include/ctws.h, ctws_filter_taps).  Host code,
+    no GPU handle."""
+    r = C.c_int(0)
+    ret = lib().ctws_filter_taps(float(sigma), int(order), None, C.byref(r))
+    if ret != CTWS_OK:
+        raise ValueError("filter_taps: sigma is positive and order is 0, 1 or 2, not %r, %r" % (sigma, order))
+    out = np.empty(2 * r.value + 1, dtype=np.float64)
+    lib().ctws_filter_taps(float(sigma), int(order), out.ctypes.data, C.byref(r))
+    return out
+
+
+def image_filter_check(filter_name, sigma, apply_in_2d=False):
+    """The refusals of the image filter, before anything is opened: -> (filter id, the three sigmas
+    z, y, x).  NotImplementedError for vigra's multi-channel filters, ValueError for any other
+    unknown name, a non-positive sigma or a sigma list together with apply_in_2d (the reference's
+    assert)."""
+    if filter_name in MULTI_CHANNEL_FILTERS:
+        raise NotImplementedError("image filter: %s gives several channels per voxel; only %s are computed"
+                                  % (filter_name, ', '.join(IMAGE_FILTERS)))
+    if filter_name not in IMAGE_FILTERS:
+        raise ValueError("image filter: unknown filter %r (one of %s)" % (filter_name, ', '.join(IMAGE_FILTERS)))
+    if isinstance(sigma, (tuple, list)):
+        if len(sigma) != 3:
+            raise ValueError("image filter: a sigma list has three values (z, y, x), not %r" % (sigma,))
+        if apply_in_2d:
+            raise ValueError("image filter: a sigma list cannot be combined with apply_in_2d")
+        sig = tuple(float(s) for s in sigma)
+    else:
+        sig = (float(sigma),) * 3
+    if not all(s > 0 and np.isfinite(s) for s in sig):
+        raise ValueError("image filter: sigma is positive, not %r" % (sigma,))
+    return IMAGE_FILTERS[filter_name], sig
 
 
 def _dtype_name(dtype):
@@ -1118,5 +1166,46 @@ class Handle:
                                                 (C.c_int64 * 3)(*fac), code, out.data_ptr(), *oshape, C.byref(flag))
         self._check(ret, 'ctws_downscale_block_device')
         return out, bool(flag.value)
+
+    # ---- ImageFilter kernels ----------------------------------------------------------------
+    IMAGE_FILTER_DTYPES = ('uint8', 'uint16', 'float32', 'float64')
+
+    @classmethod
+    def _image_filter_check(cls, dtype, shape, filter_name, sigma, apply_in_2d):
+        fid, sig = image_filter_check(filter_name, sigma, apply_in_2d)
+        if _dtype_name(dtype) not in cls.IMAGE_FILTER_DTYPES:
+            raise TypeError("image filter: the block is uint8, uint16, float32 or float64, not %s" % (dtype,))
+        shape = tuple(int(s) for s in shape)
+        if len(shape) != 3 or 0 in shape:
+            raise ValueError("image filter: the input is a non-empty 3-D block, not %s" % (shape,))
+        return fid, (C.c_double * 3)(*sig), shape
+
+    def image_filter(self, data, filter_name, sigma, apply_in_2d=False, normalize=True):
+        """One block through a Gaussian filter (include/ctws.h, ctws_image_filter): data (nz, ny, nx)
+        of uint8, uint16, float32 or float64; filter_name 'gaussianSmoothing',
+        'gaussianGradientMagnitude' or 'laplacianOfGaussian'; sigma a positive scalar or (z, y, x);
+        apply_in_2d filters every z slice on its own; normalize applies vu.normalize to the block
+        first.  -> the float32 response of the same shape.  A block shorter than a tap radius + 1
+        along a filtered axis raises CtwsError."""
+        data = np.ascontiguousarray(data)
+        fid, sig, shape = self._image_filter_check(data.dtype, data.shape, filter_name, sigma, apply_in_2d)
+        out = np.empty(shape, dtype=np.float32)
+        ret = lib().ctws_image_filter(self._h, data.ctypes.data, dtype_code(data.dtype), *shape, fid, sig,
+                                      int(bool(apply_in_2d)), int(bool(normalize)), out.ctypes.data)
+        self._check(ret, 'ctws_image_filter')
+        return out
+
+    def image_filter_device(self, data, filter_name, sigma, apply_in_2d=False, normalize=True):
+        """image_filter on a torch tensor on this GPU; the response comes back as a float32 tensor
+        on the same device: nothing crosses PCIe."""
+        import torch
+        assert data.is_cuda and data.is_contiguous()
+        fid, sig, shape = self._image_filter_check(data.dtype, data.shape, filter_name, sigma, apply_in_2d)
+        torch.cuda.current_stream(data.device).synchronize()
+        out = torch.empty(shape, dtype=torch.float32, device=data.device)
+        ret = lib().ctws_image_filter_device(self._h, data.data_ptr(), _dtype_code(data.dtype), *shape, fid, sig,
+                                             int(bool(apply_in_2d)), int(bool(normalize)), out.data_ptr())
+        self._check(ret, 'ctws_image_filter_device')
+        return out
 
     # ---- multi-GPU label-count exchange (RCCL) ------------------------------------------

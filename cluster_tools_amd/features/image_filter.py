@@ -1,0 +1,171 @@
+#! /usr/bin/env python
+"""ImageFilter: a Gaussian filter response of every block on the GPU
+(cluster_tools/features/image_filter.py:20-160; task surface, config keys, job config keys, the
+float32 gzip output dataset with chunks min(block_shape // 2, shape) and the log lines unchanged).
+The job replaces `vu.apply_filter(vu.normalize(ds_in[outer]), filter_name, sigma, apply_in_2d)`
+(:105-115): one library handle per job, outer blocks read ahead on a thread, filtered by
+`Handle.image_filter` with normalize=True, the inner box written.  gaussianSmoothing,
+gaussianGradientMagnitude and laplacianOfGaussian are computed (vigra's semantics restated; the
+reference prefers fastfilters' approximations when that library is importable, which are not).
+vigra's multi-channel filters are refused before any block is read: the reference's 3-D float32
+output dataset cannot hold them either.  A halo below a filter radius is legal, as in the
+reference: such blocks are computed with reflected borders, and the job says so once."""
+import json
+import os
+import sys
+from concurrent import futures
+
+from cluster_tools_amd import luigi_compat as luigi
+import cluster_tools_amd.utils.volume_utils as vu
+import cluster_tools_amd.utils.function_utils as fu
+from cluster_tools_amd.utils.blocking import Blocking
+from cluster_tools_amd.utils.task_utils import DummyTask
+from cluster_tools_amd.cluster_tasks import SlurmTask, LocalTask, LSFTask
+
+
+class ImageFilterBase(luigi.Task):
+    task_name = 'image_filter'
+    src_file = os.path.abspath(__file__)
+
+    input_path = luigi.Parameter()
+    input_key = luigi.Parameter()
+    output_path = luigi.Parameter()
+    output_key = luigi.Parameter()
+    filter_name = luigi.Parameter()
+    sigma = luigi.Parameter()
+    halo = luigi.ListParameter()
+    dependency = luigi.TaskParameter(default=DummyTask())
+
+    def requires(self):
+        return self.dependency
+
+    @staticmethod
+    def default_task_config():
+        config = LocalTask.default_task_config()
+        config.update({'apply_in_2d': False})
+        return config
+
+    def run_impl(self):
+        shebang, block_shape, roi_begin, roi_end = self.global_config_values()
+        self.init(shebang)
+        config = self.get_task_config()
+        sigma = list(self.sigma) if isinstance(self.sigma, (tuple, list)) else self.sigma
+        check_supported(self.filter_name, sigma, config.get('apply_in_2d', False))
+        config.update({'input_path': self.input_path, 'input_key': self.input_key,
+                       'output_path': self.output_path, 'output_key': self.output_key,
+                       'filter_name': self.filter_name, 'sigma': sigma,
+                       'halo': list(self.halo), 'block_shape': block_shape})
+        shape = vu.get_shape(self.input_path, self.input_key)
+        chunks = tuple(min(bs // 2, sh) for bs, sh in zip(block_shape, shape))
+        with vu.file_reader(self.output_path) as f:
+            f.require_dataset(self.output_key, shape=shape, dtype='float32', compression='gzip', chunks=chunks)
+        if self.n_retries == 0:
+            block_list = vu.blocks_in_volume(shape, block_shape, roi_begin, roi_end)
+        else:
+            block_list = self.block_list
+            self.clean_up_for_retry(block_list)
+        n_jobs = min(len(block_list), self.max_jobs)
+        self.prepare_jobs(n_jobs, block_list, config)
+        self.submit_jobs(n_jobs)
+        self.wait_for_jobs()
+        self.check_jobs(n_jobs)
+
+
+class ImageFilterLocal(ImageFilterBase, LocalTask):
+    pass
+
+
+class ImageFilterSlurm(ImageFilterBase, SlurmTask):
+    pass
+
+
+class ImageFilterLSF(ImageFilterBase, LSFTask):
+    pass
+
+
+#
+# Implementation
+#
+
+def check_supported(filter_name, sigma, apply_in_2d):
+    """The refusals, before anything is opened: -> (filter id, the sigmas z, y, x).
+    NotImplementedError for vigra's multi-channel filters, ValueError for an unknown name, a
+    non-positive sigma and a sigma list with apply_in_2d (the reference's assert)."""
+    from cluster_tools_amd.ctws import image_filter_check
+    return image_filter_check(filter_name, sigma, apply_in_2d)
+
+
+def filter_radii(filter_name, sigma, apply_in_2d=False):
+    """The largest tap radius per axis z, y, x (0 along z with apply_in_2d): order 0 has
+    max(1, int(3 sigma + 0.5)), the derivative of order n max(1, int((3 + n / 2) sigma + 0.5))."""
+    fid, sig = check_supported(filter_name, sigma, apply_in_2d)
+    radii = [max(1, int((3.0 + 0.5 * fid) * s + 0.5)) for s in sig]
+    if apply_in_2d:
+        radii[0] = 0
+    return radii
+
+
+def halo_warning(halo, filter_name, sigma, apply_in_2d=False):
+    """The job's warning when the halo is smaller than a filter radius, else None."""
+    radii = filter_radii(filter_name, sigma, apply_in_2d)
+    short = ['%s: halo %i < radius %i' % (a, h, r) for a, h, r in zip('zyx', halo, radii) if h < r]
+    if not short:
+        return None
+    return ("WARNING: the halo %s is smaller than the radius of %s with sigma %s (%s); the blocks are filtered "
+            "with reflected borders, as in the reference, and differ from the filter of the whole volume near "
+            "their faces" % (list(halo), filter_name, sigma, ', '.join(short)))
+
+
+def _device():
+    return int(os.environ.get('CTWS_DEVICE', os.environ.get('LOCAL_RANK', '0')))
+
+
+def run_filter_blocks(blocking, block_list, ds_in, ds_out, halo, filter_name, sigma, apply_in_2d):
+    """The filter response of every block of the job."""
+    from cluster_tools_amd import ctws
+
+    def read(block_id):
+        block = blocking.getBlockWithHalo(block_id, halo)
+        return block, ds_in[vu.block_to_bb(block.outerBlock)]
+
+    with ctws.Handle(_device()) as h, futures.ThreadPoolExecutor(1) as io:
+        nxt = io.submit(read, block_list[0]) if block_list else None
+        for k, block_id in enumerate(block_list):
+            fu.log("start processing block %i" % block_id)
+            block, data = nxt.result()
+            nxt = io.submit(read, block_list[k + 1]) if k + 1 < len(block_list) else None
+            try:
+                response = h.image_filter(data, filter_name, sigma, apply_in_2d, normalize=True)
+            except ctws.CtwsError as e:
+                raise RuntimeError("block %i (outer shape %s): %s" % (block_id, tuple(data.shape), e))
+            ds_out[vu.block_to_bb(block.innerBlock)] = response[vu.block_to_bb(block.innerBlockLocal)]
+            fu.log_block_success(block_id)
+
+
+def image_filter(job_id, config_path):
+    fu.log("start processing job %i" % job_id)
+    fu.log("reading config from %s" % config_path)
+    with open(config_path) as f:
+        config = json.load(f)
+    sigma, filter_name, halo = config['sigma'], config['filter_name'], config['halo']
+    apply_in_2d = config.get('apply_in_2d', False)
+    check_supported(filter_name, sigma, apply_in_2d)
+    warning = halo_warning(halo, filter_name, sigma, apply_in_2d)
+    if warning:
+        fu.log(warning)
+    with vu.file_reader(config['input_path'], 'r') as f_in, vu.file_reader(config['output_path']) as f_out:
+        ds_in, ds_out = f_in[config['input_key']], f_out[config['output_key']]
+        if ds_in.ndim != 3:
+            raise NotImplementedError("image_filter: the input must be 3-D, not %i-D" % ds_in.ndim)
+        if str(ds_in.dtype) not in ('uint8', 'uint16', 'float32', 'float64'):
+            raise TypeError("image_filter: the input must be uint8, uint16, float32 or float64, not %s" % ds_in.dtype)
+        blocking = Blocking([0, 0, 0], list(ds_in.shape), list(config['block_shape']))
+        run_filter_blocks(blocking, config['block_list'], ds_in, ds_out, halo, filter_name, sigma, apply_in_2d)
+    fu.log_job_success(job_id)
+
+
+if __name__ == '__main__':
+    path = sys.argv[1]
+    assert os.path.exists(path), path
+    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
+    image_filter(job_id, path)

@@ -468,6 +468,44 @@ int ctws_region_centers_device(ctws_handle* h, const uint64_t* labels, int64_t n
                                uint8_t* found);
 
 /*
+ * ImageFilter (features/image_filter.py:105-115): vigra's Gaussian filters of one block, restated
+ * (vigra is not available, parity at its boundary is unpinned).
+ *
+ * ctws_filter_taps: host code, no handle.  The 2 r + 1 taps for the offsets -r .. r of the Gaussian
+ *   (order 0: radius int(3 sigma + 0.5), at least 1, taps summing to 1) or of its first or second
+ *   derivative (order n: radius max(1, int((3 + n / 2) sigma + 0.5)), raw(x) = -x e(x) or
+ *   (x^2 / sigma^2 - 1) e(x) with e(x) = exp(-x^2 / (2 sigma^2)), minus the mean of the raw values,
+ *   scaled so that sum_x k(x) (-x)^n / n! = 1).  *radius = r always; out may be NULL (the radius
+ *   alone), else it holds 2 r + 1 doubles.  CTWS_EINVAL for sigma <= 0, NaN or an order outside 0..2.
+ *
+ * ctws_image_filter / _device: data = one block (nz, ny, nx), C order, of dtype CTWS_U8, CTWS_U16,
+ *   CTWS_F32 or CTWS_F64; out = float32 of the same shape.
+ *     f       = float32(data); with normalize: f -= min(f); m = max(f); f /= m when m > 0
+ *             (vu.normalize, float32 arithmetic)
+ *     conv    along one axis with taps k of radius r: out[i] = float32(sum over p = i - r .. i + r
+ *             ascending of k[i - p] * double(in[reflect(p)])), reflect(p) = -p or 2 (L - 1) - p,
+ *             multiply and add separate, float32 between the axes, axes in the order z, y, x
+ *     filter_id 0 gaussianSmoothing: S S S (S: order 0 along an axis, sigma[axis])
+ *             1 gaussianGradientMagnitude: g_z = S_x S_y D_z, g_y = S_x D_y S_z, g_x = D_x S_y S_z
+ *               (D: order 1); out = sqrtf((g_z g_z + g_y g_y) + g_x g_x) in float32, the square
+ *               root correctly rounded
+ *             2 laplacianOfGaussian: the same with the order-2 taps; out = (l_z + l_y) + l_x
+ *     apply_in_2d: every z slice on its own -- the y and x passes alone, two components;
+ *             sigma[0] is not read
+ *   CTWS_EINVAL when an axis holds fewer voxels than a radius + 1 along it (the message names the
+ *   axis and the radius; vigra refuses such a line), CTWS_EUNSUPPORTED for a radius above 48 or
+ *   2^31 or more voxels.  Scratch of the handle: 8 (smoothing) or 20 bytes per voxel.  No
+ *   floating-point atomics: the result depends on the inputs alone, and host and device pointers
+ *   give the same bits.  ctws_last_timings reports if_minmax, if_first, if_y, if_x.  Host pointers
+ *   are staged through HBM; _device takes device pointers on the handle's GPU for data and out.
+ */
+int ctws_filter_taps(double sigma, int order, double* out, int* radius);
+int ctws_image_filter(ctws_handle* h, const void* data, int dtype, int64_t nz, int64_t ny, int64_t nx, int filter_id,
+                      const double sigma[3], int apply_in_2d, int normalize, float* out);
+int ctws_image_filter_device(ctws_handle* h, const void* data, int dtype, int64_t nz, int64_t ny, int64_t nx,
+                             int filter_id, const double sigma[3], int apply_in_2d, int normalize, float* out);
+
+/*
  * EdgeFeaturesWorkflow (features/features_workflow.py:14-66), BlockEdgeFeatures: the boundary-map
  * statistics of the edges of one block (block_edge_features.py:113-132,
  * `ndist.extractBlockFeaturesFromBoundaryMaps_*`, restated: DESIGN.md section 3.5).
