@@ -171,6 +171,9 @@ struct ctws_handle {
     int trace = 0;       // CTWS_TRACE=1: per-round flood statistics on stderr
     int no_descent = 0;  // CTWS_NO_DESCENT=1: flood from the seeds alone (test hook)
     int seed_tilecc = 0;  // CTWS_SEED_TILECC=1: the seed CC by tiles (else k_seed_members / k_seed_union2)
+    // CTWS_SEED_DENSE=1: k_seed_members / k_plateau_flag over every class byte instead of the walk
+    // over k_localmax's equal bitmap (k_seed_members_eq / k_plateau_flag_eq)
+    int seed_dense = 0;
     int no_fallback = 0; // CTWS_NO_FALLBACK=1: keep a failed descent result (debugging)
     // CTWS_FORCE_WIDE=1: every flood on the wide keys (k_flood, 32-bit d; tests).  wide_rerun:
     // run_batch is re-running blocks whose packed flood reported a saturated d (dsat)
@@ -1227,6 +1230,8 @@ int run_batch(ctws_handle* h, const ctws_cfg* cfg, const Plan& pl, ctws_block* b
     mark("prep_edt_x");
     set_timing(h, "prep_kernel", (float)prep_kernel);
     bool packed = true;
+    // the seed stage's passes over the classes: dense, or a walk over k_localmax's equal bitmap
+    const bool seed_dense = !pl.from_seeds && (h->seed_dense || h->seed_tilecc);
     uint32_t max_seeds = 0;  // sizes the LDS histogram of the size filter
     std::vector<BlockStat> s2(nb);
     const dim3 gsb((unsigned)((maxZ + 255) / 256), nb);
@@ -1360,40 +1365,59 @@ int run_batch(ctws_handle* h, const ctws_cfg* cfg, const Plan& pl, ctws_block* b
     // ---- seeds: local maxima, plateaus, CC, vigra scan-order ids -----------------------------
     {
         HIPCHK(hipMemsetAsync(h->ptile.p, 0, sizeof(uint32_t) * (size_t)std::max<int64_t>(TPT, 1), h->stream));
-        k_localmax<<<wtg, 256, 0, h->stream>>>(w.desc, w.stat, seedmap, w.cls, w.smax, (uint32_t*)h->ptile.p);
+        // k_localmax also writes the member bitmap, the strict maxima's forest entries and the
+        // equal bitmap (in w.fopen: free until the flood), and the plateau kernels walk the
+        // equal bitmap; the dense kernels read every class instead (CTWS_SEED_DENSE=1, and the
+        // tile CC, which builds the member bitmap with atomicOr on a zeroed one)
+        const bool dense = seed_dense;
+        uint64_t* const feq = w.fopen;
+        if (dense) k_localmax<<<wtg, 256, 0, h->stream>>>(w.desc, w.stat, seedmap, w.cls, w.smax, (uint32_t*)h->ptile.p,
+                                                         nullptr, nullptr, nullptr);
+        else k_localmax<<<wtg, 256, 0, h->stream>>>(w.desc, w.stat, seedmap, w.cls, w.smax, (uint32_t*)h->ptile.p,
+                                                    w.fseed, feq, w.PF);
         LAUNCHCHK();
         // plateaus (equal-valued maxima candidates) and the seed CC: LDS tile union-find
         // (k_tilecc.hip); blocks without plateau voxels skip the plateau kernels on the device
         // the seed CC's member bitmap (CcArgs::troot for SEED): its parents are members-only
-        HIPCHK(hipMemsetAsync(w.fseed, 0, sizeof(uint64_t) * (size_t)TF, h->stream));
+        if (dense) HIPCHK(hipMemsetAsync(w.fseed, 0, sizeof(uint64_t) * (size_t)TF, h->stream));
         CcArgs ca{seedmap, w.cls, w.P, nullptr, nullptr, 0, w.fseed, nullptr, (const uint32_t*)h->ptile.p};
+        // one wave per 64 words of the equal bitmap
+        const dim3 eg((unsigned)std::min<int64_t>((maxRows * ((maxX + 63) / 64) + 255) / 256, 2048), nb);
         if (pl.nd_ws == 3) {
             using T = CcTileM<3, CC_SEED>;  // (= the plateau tile)
             const dim3 tg(tiles8(cdiv(maxZ, T::TZ) * cdiv(maxY, T::TY) * cdiv(maxX, T::TX)), nb);
             k_tile_cc<3, CC_PLATEAU><<<tg, 256, 0, h->stream>>>(w.desc, w.stat, ca, w.P);
             k_tile_merge<3, CC_PLATEAU><<<dim3(std::min(tg.x, 2048u), tg.y), 256, 0, h->stream>>>(w.desc, w.stat, ca, w.P);
-            k_plateau_flag<<<vg, 256, 0, h->stream>>>(w.desc, w.stat, w.cls, w.P);
+            if (dense) k_plateau_flag<<<vg, 256, 0, h->stream>>>(w.desc, w.stat, w.cls, w.P);
+            else k_plateau_flag_eq<<<eg, 256, 0, h->stream>>>(w.desc, w.stat, w.cls, w.P, feq);
             if (h->seed_tilecc) {
                 k_tile_cc<3, CC_SEED><<<tg, 256, 0, h->stream>>>(w.desc, w.stat, ca, w.PF);
                 k_tile_merge<3, CC_SEED><<<dim3(std::min(tg.x, 2048u), tg.y), 256, 0, h->stream>>>(w.desc, w.stat, ca, w.PF);
-            } else {
+            } else if (dense) {
                 // the seed components are the maximal plateaus and the isolated maxima (k_cc.hip)
                 k_seed_members<3><<<wtg, 256, 0, h->stream>>>(w.desc, w.stat, w.cls, w.P, w.PF, w.fseed, nullptr);
+            } else {
+                k_seed_members_eq<3><<<eg, 256, 0, h->stream>>>(w.desc, w.stat, w.cls, w.P, w.PF, w.fseed, feq, nullptr);
             }
         } else {
             using T = CcTile<2>;
             const dim3 tg(tiles8(cdiv(maxZ, T::TZ) * cdiv(maxY, T::TY) * cdiv(maxX, T::TX)), nb);
             k_tile_cc<2, CC_PLATEAU><<<tg, 256, 0, h->stream>>>(w.desc, w.stat, ca, w.P);
             k_tile_merge<2, CC_PLATEAU><<<dim3(std::min(tg.x, 2048u), tg.y), 256, 0, h->stream>>>(w.desc, w.stat, ca, w.P);
-            k_plateau_flag<<<vg, 256, 0, h->stream>>>(w.desc, w.stat, w.cls, w.P);
+            if (dense) k_plateau_flag<<<vg, 256, 0, h->stream>>>(w.desc, w.stat, w.cls, w.P);
+            else k_plateau_flag_eq<<<eg, 256, 0, h->stream>>>(w.desc, w.stat, w.cls, w.P, feq);
             if (h->seed_tilecc) {
                 k_tile_cc<2, CC_SEED><<<tg, 256, 0, h->stream>>>(w.desc, w.stat, ca, w.PF);
                 k_tile_merge<2, CC_SEED><<<dim3(std::min(tg.x, 2048u), tg.y), 256, 0, h->stream>>>(w.desc, w.stat, ca, w.PF);
             } else {
                 // every maximum its own root; the plateau maxima listed (in w.A, free until the size
                 // filter) and united with their 4-adjacent maxima (k_cc.hip)
-                k_seed_members<2><<<wtg, 256, 0, h->stream>>>(w.desc, w.stat, w.cls, w.P, w.PF, w.fseed,
-                                                             (uint32_t*)w.A);
+                if (dense)
+                    k_seed_members<2><<<wtg, 256, 0, h->stream>>>(w.desc, w.stat, w.cls, w.P, w.PF, w.fseed,
+                                                                 (uint32_t*)w.A);
+                else
+                    k_seed_members_eq<2><<<eg, 256, 0, h->stream>>>(w.desc, w.stat, w.cls, w.P, w.PF, w.fseed, feq,
+                                                                   (uint32_t*)w.A);
                 k_seed_union2<<<dim3(64, nb), 256, 0, h->stream>>>(w.desc, w.stat, w.cls, w.P, (const uint32_t*)w.A,
                                                                    w.PF);
             }
@@ -1915,6 +1939,8 @@ int run_batch(ctws_handle* h, const ctws_cfg* cfg, const Plan& pl, ctws_block* b
     add_timing(h, "sf_sparse_blocks", (float)n_sf_sparse);
     add_timing(h, "sf_redo_blocks", (float)n_sf_redo);
     add_timing(h, "hist_fused", counts_ready ? 1.f : 0.f);  // batches whose flood check counted the labels
+    // batches whose seed stage read every class byte again (CTWS_SEED_DENSE=1, CTWS_SEED_TILECC=1)
+    add_timing(h, "seed_dense", seed_dense ? 1.f : 0.f);
     add_timing(h, "flood_kernel_ms", fk1);
     add_timing(h, "flood_packed", packed ? 1.f : 0.f);
     add_timing(h, "flood_tiles_solved", (float)h->flood_tiles);
@@ -2541,6 +2567,7 @@ int ctws_open(int device, ctws_handle** out) {
     if (const char* t = std::getenv("CTWS_TRACE")) h->trace = std::atoi(t);
     if (const char* t = std::getenv("CTWS_NO_DESCENT")) h->no_descent = std::atoi(t);
     if (const char* t = std::getenv("CTWS_SEED_TILECC")) h->seed_tilecc = std::atoi(t);
+    if (const char* t = std::getenv("CTWS_SEED_DENSE")) h->seed_dense = std::atoi(t);
     if (const char* t = std::getenv("CTWS_NO_FALLBACK")) h->no_fallback = std::atoi(t);
     if (const char* t = std::getenv("CTWS_FORCE_WIDE")) h->force_wide = std::atoi(t);
     if (const char* t = std::getenv("CTWS_SF_SPARSE")) h->sf_sparse = std::atoi(t);

@@ -91,8 +91,13 @@ __global__ void k_gauss_yx(const BlockDesc*, const BlockStat*, int, HmapParams, 
                            const float*, const float*, const uint32_t*, const uint32_t*, float*);
 
 // k_cc.hip
-__global__ void k_localmax(const BlockDesc*, BlockStat*, const float*, uint8_t*, const uint32_t*, uint32_t*);
+__global__ void k_localmax(const BlockDesc*, BlockStat*, const float*, uint8_t*, const uint32_t*, uint32_t*, uint64_t*,
+                           uint64_t*, uint32_t*);
 __global__ void k_plateau_flag(const BlockDesc*, const BlockStat*, uint8_t*, uint32_t*);
+__global__ void k_plateau_flag_eq(const BlockDesc*, const BlockStat*, uint8_t*, uint32_t*, const uint64_t*);
+template <int ND>
+__global__ void k_seed_members_eq(const BlockDesc*, BlockStat*, const uint8_t*, const uint32_t*, uint32_t*, uint64_t*,
+                                  const uint64_t*, uint32_t*);
 __global__ void k_flatten_tile_roots(const BlockDesc*, const BlockStat*, uint32_t*, const uint64_t*, uint64_t*);
 __global__ void k_flatten_seeds(const BlockDesc*, const BlockStat*, uint32_t*, const uint64_t*, uint64_t*);
 template <int ND>

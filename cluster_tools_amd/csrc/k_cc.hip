@@ -62,10 +62,18 @@ namespace ctws {
 // its neighbours.  Those voxels are classified "greater neighbour" outright and stay out of
 // the plateau union-find (the masked region of a masked block — fin = 1, dt = 0 — is one
 // huge zero plateau otherwise).  pos: the slice's / block's dt maximum > 0.
+//
+// Bitmaps (fseed != nullptr): gt and eq of a row's word sit in the lanes, so the wave also
+// stores, per (row, word) and in the frontier layout (fbase), the ballot of the strict maxima
+// (no greater, no equal neighbour) into fseed and of the plateau voxels into feq, and the strict
+// maxima's seed-forest entries PF[i] = i.  Every in-block word of both bitmaps is written exactly
+// once (no memset); a word without a plateau voxel is then final, and k_seed_members_eq /
+// k_plateau_flag_eq visit the others only.
 template <int ND>
 __device__ __forceinline__ void localmax_words(const BlockDesc& B, const BlockStat& st, const uint32_t* __restrict__ smax,
                                                const float* __restrict__ p, uint8_t* __restrict__ cl, uint32_t& nplat,
-                                               uint32_t* __restrict__ ptile) {
+                                               uint32_t* __restrict__ ptile, uint64_t* __restrict__ fseed,
+                                               uint64_t* __restrict__ feq, uint32_t* __restrict__ PF) {
     const uint32_t ord0 = 0x80000000u;  // ordf(+0.0f)
     constexpr int U = 8, R = U + 2;
     const int Y = B.Y, X = B.X, Z = B.Z;
@@ -167,6 +175,18 @@ __device__ __forceinline__ void localmax_words(const BlockDesc& B, const BlockSt
             if (valid) cl[zb + (int64_t)y * X + x] = (uint8_t)((gt ? 1 : 0) | (eq ? 2 : 0));
             nplat += valid && eq;  // plateau parents: k_tile_cc<.., CC_PLATEAU> (k_tilecc.hip)
             ueq |= valid && eq;
+            if (fseed) {
+                // the row's words of the member and the equal bitmaps, and the strict maxima's
+                // seed-forest entries (their own roots): see k_seed_members_eq
+                const bool smx = valid && !gt && !eq;
+                const uint64_t ms = __ballot(smx), me = __ballot(valid && eq);
+                if (y < Y && lane == 0) {
+                    const int64_t fw = B.fbase + ((int64_t)z * Y + y) * wpr + xw;
+                    fseed[fw] = ms;
+                    feq[fw] = me;
+                }
+                if (smx) PF[zb + (int64_t)y * X + x] = (uint32_t)(zb + (int64_t)y * X + x);
+            }
         }
         // the plateau CC's tiles that hold a plateau voxel (CcTileM<ND, CC_PLATEAU>: 2-D
         // 1 x 32 x 64, one word column; 3-D 8 x 16 x 32, two tiles per word): the others are
@@ -187,12 +207,15 @@ __device__ __forceinline__ void localmax_words(const BlockDesc& B, const BlockSt
 
 __global__ void __launch_bounds__(256) k_localmax(const BlockDesc* __restrict__ D, BlockStat* S,
                                                   const float* __restrict__ v, uint8_t* __restrict__ cls,
-                                                  const uint32_t* __restrict__ smax, uint32_t* __restrict__ ptile) {
+                                                  const uint32_t* __restrict__ smax, uint32_t* __restrict__ ptile,
+                                                  uint64_t* __restrict__ fseed, uint64_t* __restrict__ feq,
+                                                  uint32_t* __restrict__ PFg) {
     const BlockDesc& B = D[blockIdx.y];
     if (!S[blockIdx.y].active) return;
     uint32_t nplat = 0;
-    if (B.nd_ws == 3) localmax_words<3>(B, S[blockIdx.y], smax, v + B.base, cls + B.base, nplat, ptile);
-    else localmax_words<2>(B, S[blockIdx.y], smax, v + B.base, cls + B.base, nplat, ptile);
+    uint32_t* PF = PFg ? PFg + B.base : nullptr;
+    if (B.nd_ws == 3) localmax_words<3>(B, S[blockIdx.y], smax, v + B.base, cls + B.base, nplat, ptile, fseed, feq, PF);
+    else localmax_words<2>(B, S[blockIdx.y], smax, v + B.base, cls + B.base, nplat, ptile, fseed, feq, PF);
     nplat = wg_reduce_u32(nplat, OpAdd());
     if (threadIdx.x == 0 && nplat) atomicAdd(&S[blockIdx.y].plateau, nplat);
 }
@@ -358,6 +381,97 @@ __global__ void __launch_bounds__(256) k_plateau_flag(const BlockDesc* __restric
             }
         }
     }
+}
+
+// The walk of k_seed_members_eq / k_plateau_flag_eq over the equal bitmap of k_localmax (one
+// word per (row, 64-voxel word), frontier layout): a wave loads 64 words, one per lane, and for
+// every non-zero one the whole wave runs BODY with lane = voxel.  BODY sees w (the word's index in
+// the block), x, valid (x < X), gi (block C-order index, 0 where invalid) and c (the voxel's
+// class; 1, "greater neighbour", where invalid).  Smoothed float seed maps have next to no
+// equal voxel, so the walk is the bitmap's 1/8 byte per voxel and little else.
+#define EQ_WORDS(B, feq, cl, ...)                                                                \
+    {                                                                                             \
+        const int wpr = ((B).X + 63) >> 6;                                                        \
+        const int64_t nwords_ = (int64_t)(B).Z * (B).Y * wpr;                                     \
+        const int lane = threadIdx.x & 63;                                                        \
+        const int64_t nwaves_ = (int64_t)gridDim.x * (blockDim.x >> 6);                           \
+        const int64_t wave_ = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);       \
+        for (int64_t w0_ = wave_ * 64; w0_ < nwords_; w0_ += nwaves_ * 64) {                      \
+            const uint64_t e_ = w0_ + lane < nwords_ ? gbl(feq)[(B).fbase + w0_ + lane] : 0ull;   \
+            uint64_t nz_ = __ballot(e_ != 0ull);                                                  \
+            while (nz_) {                                                                         \
+                const int64_t w = w0_ + __builtin_ctzll(nz_);                                     \
+                nz_ &= nz_ - 1ull;                                                                \
+                const uint32_t row_ = (uint32_t)w / (uint32_t)wpr;                                \
+                const int x = ((int)((uint32_t)w - row_ * (uint32_t)wpr) << 6) + lane;            \
+                const bool valid = x < (B).X;                                                     \
+                const int64_t gi = valid ? (int64_t)row_ * (B).X + x : 0;                         \
+                const uint8_t c = valid ? (cl)[gi] : (uint8_t)1;                                  \
+                __VA_ARGS__                                                                       \
+            }                                                                                     \
+        }                                                                                         \
+    }
+
+// k_seed_members on the words that hold a plateau voxel.  k_localmax has written the member
+// bitmap and the forest entries of the strict maxima; a word with an equal voxel is redone here
+// whole, as k_seed_members does it: its plateau voxels without a greater neighbour are members iff
+// their plateau's root is not flagged (k_plateau_flag_eq), 3-D under the plateau's root, 2-D their
+// own roots and listed for k_seed_union2.  Blocks without a plateau voxel return at once.
+template <int ND>
+__global__ void __launch_bounds__(256) k_seed_members_eq(const BlockDesc* __restrict__ D, BlockStat* S,
+                                                         const uint8_t* __restrict__ cls, const uint32_t* __restrict__ Pp,
+                                                         uint32_t* __restrict__ PFg, uint64_t* __restrict__ fseed,
+                                                         const uint64_t* __restrict__ feq, uint32_t* __restrict__ plist) {
+    const BlockDesc& B = D[blockIdx.y];
+    BlockStat& st = S[blockIdx.y];
+    if (!st.active || !st.plateau) return;
+    const uint8_t* cl = cls + B.base;
+    const uint32_t* PP = Pp + B.base;
+    uint32_t* PF = PFg + B.base;
+    EQ_WORDS(B, feq, cl, {
+        bool mx = !(c & 1);
+        uint32_t par = (uint32_t)gi;
+        bool listed = false;
+        if (mx && (c & 2)) {  // cc_is_max of a plateau voxel
+            const uint32_t r = uf_find(PP, par);
+            if (cl[r] & 4) mx = false;
+            else if (ND == 3) par = r;
+            else listed = true;
+        }
+        const uint64_t m = __ballot(mx);
+        if (lane == 0) fseed[B.fbase + w] = m;
+        if (mx) PF[gi] = par;
+        if (ND == 2) {
+            const uint64_t lm = __ballot(listed);
+            if (lm) {
+                uint32_t base = 0;
+                if (lane == 0) base = atomicAdd(&st._u, (uint32_t)__popcll(lm));
+                base = (uint32_t)__shfl((int)base, 0);
+                if (listed) plist[B.base + base + __popcll(lm & ((1ull << lane) - 1ull))] = par;
+            }
+        }
+    })
+}
+template __global__ void k_seed_members_eq<2>(const BlockDesc*, BlockStat*, const uint8_t*, const uint32_t*, uint32_t*,
+                                              uint64_t*, const uint64_t*, uint32_t*);
+template __global__ void k_seed_members_eq<3>(const BlockDesc*, BlockStat*, const uint8_t*, const uint32_t*, uint32_t*,
+                                              uint64_t*, const uint64_t*, uint32_t*);
+
+// k_plateau_flag on the words that hold a plateau voxel (the equal bitmap of k_localmax)
+__global__ void __launch_bounds__(256) k_plateau_flag_eq(const BlockDesc* __restrict__ D, const BlockStat* S,
+                                                         uint8_t* __restrict__ cls, uint32_t* __restrict__ Pg,
+                                                         const uint64_t* __restrict__ feq) {
+    const BlockDesc& B = D[blockIdx.y];
+    if (!S[blockIdx.y].active || !S[blockIdx.y].plateau) return;
+    uint8_t* cl = cls + B.base;
+    uint32_t* P = Pg + B.base;
+    EQ_WORDS(B, feq, cl, {
+        (void)w;
+        if ((c & 3) == 3) {
+            const uint32_t r = uf_find_compress(P, (uint32_t)gi);
+            cl[r] |= 4;  // benign race: every writer sets the same bit
+        }
+    })
 }
 
 // ---- root bitmap + exclusive prefix -----------------------------------------------------

@@ -236,7 +236,7 @@ int ctws_eval_end(ctws_handle* h, double* scores /* [4] */, int64_t* n_points);
  * Stage timings of the last ctws_ws_blocks* call, measured with HIP events on the
  * handle's stream (milliseconds).  names[i] is a static string.  Returns the count.
  * Some entries are counters, not times, summed over the call's batches (flood_rounds,
- * flood_packed, sf_sparse_blocks, sf_redo_blocks, hist_fused, host_batches, ...).  One names a kernel and is
+ * flood_packed, sf_sparse_blocks, sf_redo_blocks, hist_fused, seed_dense, host_batches, ...).  One names a kernel and is
  * that of the call's last batch: prep_kernel, the normalize + EDT x pass --
  *     0            the generic LDS row kernel k_prep_edt_x (4-D input, rows > 1024 voxels,
  *                  blocks of different dtypes in one batch) with the generic k_input_minmax
