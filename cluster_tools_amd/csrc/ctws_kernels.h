@@ -458,6 +458,44 @@ __global__ void k_ef_samples(EfArgs);
 __global__ void k_ef_stats(const uint64_t*, uint32_t, uint32_t, double*);
 hipError_t ef_sort(void* tmp, size_t& bytes, const uint64_t* keys_in, uint64_t* keys_out, int64_t n, int end_bit,
                    hipStream_t stream);
+// k_lifted.hip (LiftedFeaturesFromNodeLabelsWorkflow: the sparse lifted neighbourhood of a graph)
+constexpr int kLfWaves = 4;          // waves (= sources in flight) per workgroup of k_lf_bfs
+constexpr int kLfHashBits = 11;
+constexpr int kLfHashSlots = 1 << kLfHashBits;  // words of a wave's visited hash set in LDS
+constexpr int kLfHashFill = 1536;    // nodes a wave's hash set takes before the wave moves to its bitmap
+constexpr int kLfProbe = 32;         // slots an insertion looks at before it gives up (then the bitmap)
+constexpr int kLfQueueLds = 1024;    // entries of a wave's node list in LDS; the rest in its global queue
+constexpr int kLfStage = 128;        // staged keys per wave (a step emits at most 64)
+constexpr int kLfModeAll = 0, kLfModeSame = 1, kLfModeDifferent = 2;
+// the words of k_lf_degrees' counter block
+constexpr int kLfBadId = 0, kLfBadUv = 1, kLfBadOrder = 2;
+struct LfArgs {
+    const uint32_t* row;        // CSR of both directions: the list of node i is adj[row[i] .. row[i + 1])
+    const uint32_t* adj;
+    const uint64_t* lab;        // the node labels, (n)
+    const uint32_t* src;        // the labelled nodes
+    uint32_t ns;
+    uint32_t depth;             // >= 1
+    int mode;                   // kLfModeAll / Same / Different
+    uint64_t ignore;            // the label of an unlabelled node
+    int b;                      // bits per node id: a key is source << b | node
+    uint32_t* queue;            // per wave qstride words: its node list past the LDS part
+    uint32_t qstride;
+    uint32_t* bits;             // per wave bstride words: a bitmap over the nodes, zero between sources
+    uint32_t bstride;
+    uint64_t* keys;             // out
+    unsigned long long cap;     // keys at positions >= cap are counted, not written
+    unsigned long long* count;  // the append counter
+    unsigned long long* visits; // the adjacency entries looked at, summed over the waves
+};
+__global__ void k_lf_degrees(const uint64_t*, uint32_t, uint64_t, uint32_t*, unsigned long long*);
+__global__ void k_lf_fill(const uint64_t*, uint32_t, const uint32_t*, uint32_t*, uint32_t*);
+__global__ void k_lf_sources(const uint64_t*, uint32_t, uint64_t, uint32_t*, unsigned long long*);
+__global__ void k_lf_bfs(LfArgs);
+__global__ void k_lf_unpack(const uint64_t*, int64_t, int, uint64_t*);
+hipError_t lf_scan(void* tmp, size_t& bytes, const uint32_t* in, uint32_t* out, int64_t n, hipStream_t stream);
+hipError_t lf_sort(void* tmp, size_t& bytes, const uint64_t* keys_in, uint64_t* keys_out, int64_t n, int end_bit,
+                   hipStream_t stream);
 
 // k_threshcc.hip (ThresholdedComponents: BlockComponents)
 struct TcParams {

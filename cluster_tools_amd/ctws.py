@@ -94,6 +94,10 @@ def lib():
             for fn in ('ctws_edge_features_block', 'ctws_edge_features_block_device'):
                 getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_int64] * 6 + [
                     C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]
+            for fn in ('ctws_lifted_neighborhood', 'ctws_lifted_neighborhood_device'):
+                getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int,
+                                           C.c_uint64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+            L.ctws_lifted_limits.argtypes = [C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
             L.ctws_threshold_components.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                                     C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p,
                                                     C.POINTER(C.c_int64)]
@@ -123,7 +127,8 @@ EXPORTED_SYMBOLS = ('ctws_abi_version', 'ctws_open', 'ctws_close', 'ctws_last_er
                     'ctws_label_overlaps_device', 'ctws_block_morphology', 'ctws_block_morphology_device',
                     'ctws_region_features_block', 'ctws_region_features_block_device', 'ctws_downscale_block',
                     'ctws_downscale_block_device', 'ctws_region_centers', 'ctws_region_centers_device',
-                    'ctws_filter_taps', 'ctws_image_filter', 'ctws_image_filter_device')
+                    'ctws_filter_taps', 'ctws_image_filter', 'ctws_image_filter_device', 'ctws_lifted_neighborhood',
+                    'ctws_lifted_neighborhood_device', 'ctws_lifted_limits')
 
 
 def ufd_find(n_labels, pairs):
@@ -183,6 +188,33 @@ def image_filter_check(filter_name, sigma, apply_in_2d=False):
     if not all(s > 0 and np.isfinite(s) for s in sig):
         raise ValueError("image filter: sigma is positive, not %r" % (sigma,))
     return IMAGE_FILTERS[filter_name], sig
+
+
+# SparseLiftedNeighborhood: the modes of the lifted neighbourhood (include/ctws.h, CTWS_LIFTED_*)
+LIFTED_MODES = {'all': 0, 'same': 1, 'different': 2}
+
+
+def lifted_check(depth, mode):
+    """The refusals of the lifted neighbourhood before the call: -> (depth, mode code).  ValueError
+    for a depth below 1 (or no integer) and for a mode other than 'all', 'same', 'different'."""
+    if mode not in LIFTED_MODES:
+        raise ValueError("lifted neighborhood: unknown mode %r (one of %s)" % (mode, ', '.join(LIFTED_MODES)))
+    if isinstance(depth, bool) or int(depth) != depth or depth < 1:
+        raise ValueError("lifted neighborhood: depth is an integer >= 1, not %r" % (depth,))
+    if depth >= 2 ** 31:
+        raise ValueError("lifted neighborhood: depth %r does not fit 31 bits" % (depth,))
+    return int(depth), LIFTED_MODES[mode]
+
+
+def lifted_limits(n_sources=0):
+    """(first capacity, visited capacity) of the lifted neighbourhood's search (include/ctws.h,
+    ctws_lifted_limits): the keys its first pass has room for with n_sources labelled nodes, and
+    the nodes a wave's on-chip visited set takes.  Host code, no GPU handle."""
+    first, visited = C.c_int64(0), C.c_int64(0)
+    ret = lib().ctws_lifted_limits(int(n_sources), C.byref(first), C.byref(visited))
+    if ret != CTWS_OK:
+        raise ValueError("lifted_limits: n_sources is not negative, not %r" % (n_sources,))
+    return int(first.value), int(visited.value)
 
 
 def _dtype_name(dtype):
@@ -806,6 +838,63 @@ class Handle:
                                                           edges.data_ptr(), m, out.data_ptr(), C.byref(miss)),
                     'ctws_edge_features_block_device')
         return out, int(miss.value)
+
+    # ---- LiftedFeaturesFromNodeLabelsWorkflow kernels ---------------------------------------
+    # The first capacity of lifted_neighborhood in rows is the library's own first capacity for its
+    # keys, 64 per labelled node (lifted_limits): a call that does not fit computes everything again
+
+    def lifted_neighborhood_raw(self, edges, node_labels, depth, mode, ignore_label, cap):
+        """One ctws_lifted_neighborhood call with an output of `cap` rows: (return code, n_out,
+        out (cap, 2)).  depth and mode as the C call takes them."""
+        edges = np.ascontiguousarray(edges, dtype=np.uint64).reshape(-1, 2)
+        node_labels = np.ascontiguousarray(node_labels, dtype=np.uint64).ravel()
+        out = np.empty((cap, 2), dtype=np.uint64)
+        n = C.c_int64(0)
+        ret = lib().ctws_lifted_neighborhood(self._h, edges.ctypes.data if len(edges) else None, len(edges),
+                                             node_labels.ctypes.data if node_labels.size else None,
+                                             node_labels.size, depth, mode, int(ignore_label) & 0xFFFFFFFFFFFFFFFF,
+                                             out.ctypes.data if cap else None, cap, C.byref(n))
+        return ret, int(n.value), out
+
+    def lifted_neighborhood(self, edges, node_labels, depth, mode='all', ignore_label=0):
+        """The lifted edges of a graph under a node labelling (include/ctws.h,
+        ctws_lifted_neighborhood): edges (m, 2) uint64 is the merged graph's edge table (u < v, rows
+        sorted, unique), node_labels (n,) uint64 is indexed by node id.  -> (k, 2) uint64, sorted:
+        the pairs u < v of nodes whose labels both differ from ignore_label, at hop distance
+        2 .. depth in the whole graph, with equal labels (mode 'same'), unequal labels
+        ('different') or either ('all').  ValueError for a bad depth or mode before the call.  A
+        call that hits the capacity is repeated once with the returned size."""
+        depth, code = lifted_check(depth, mode)
+        node_labels = np.ascontiguousarray(node_labels, dtype=np.uint64).ravel()
+        n_sources = int(np.count_nonzero(node_labels != np.uint64(int(ignore_label) & 0xFFFFFFFFFFFFFFFF)))
+        k, out = self._call_sized(
+            'ctws_lifted_neighborhood', (lifted_limits(n_sources)[0],),
+            lambda cap: self.lifted_neighborhood_raw(edges, node_labels, depth, code, ignore_label, cap))
+        return out[:k]
+
+    def lifted_neighborhood_device(self, edges, node_labels, depth, mode='all', ignore_label=0):
+        """lifted_neighborhood on two uint64 / int64 torch tensors on this GPU; the rows come back
+        as an int64 tensor (uint64 bits) on the same device: only their number crosses PCIe."""
+        import torch
+        depth, code = lifted_check(depth, mode)
+        for t in (edges, node_labels):
+            assert t.is_cuda and t.is_contiguous() and t.element_size() == 8 and not t.is_floating_point()
+        assert edges.numel() % 2 == 0, edges.shape
+        torch.cuda.current_stream(edges.device).synchronize()
+        n = C.c_int64(0)
+        m = edges.numel() // 2
+        ignore = int(ignore_label) & 0xFFFFFFFFFFFFFFFF
+        signed = ignore - (1 << 64) if ignore >= 1 << 63 and node_labels.dtype == torch.int64 else ignore
+        n_sources = int((node_labels != signed).sum().item()) if node_labels.numel() else 0
+
+        def call(cap):
+            out = torch.empty((cap, 2), dtype=torch.int64, device=edges.device)
+            ret = lib().ctws_lifted_neighborhood_device(
+                self._h, edges.data_ptr() if m else None, m, node_labels.data_ptr() if node_labels.numel() else None,
+                node_labels.numel(), depth, code, ignore, out.data_ptr(), cap, C.byref(n))
+            return ret, n.value, out
+        k, out = self._call_sized('ctws_lifted_neighborhood_device', (lifted_limits(n_sources)[0],), call)
+        return out[:k]
 
     # ---- NodeLabelWorkflow kernels ---------------------------------------------------------
     # first capacity of label_overlaps in rows: a call that does not fit computes everything again

@@ -544,6 +544,44 @@ int ctws_edge_features_block_device(ctws_handle* h, const uint64_t* labels, cons
                                     int64_t n_edges, double* out, int64_t* n_missing);
 
 /*
+ * LiftedFeaturesFromNodeLabelsWorkflow (lifted_features/lifted_feature_workflow.py:80-198),
+ * SparseLiftedNeighborhood: the lifted edges of a graph under a node labelling
+ * (sparse_lifted_neighborhood.py:131-135, `ndist.computeLiftedNeighborhoodFromNodeLabels`, decided
+ * here: DESIGN.md section 3.12).
+ *
+ * ctws_lifted_neighborhood / _device: edges (n_edges x 2) is the merged graph's edge table: u < v in
+ *   every row, rows strictly ascending in (u, v), every id below n_nodes.  node_labels (n_nodes) is
+ *   indexed by node id; a node whose label equals ignore_label is unlabelled.  depth >= 1.
+ *   mode: CTWS_LIFTED_ALL, CTWS_LIFTED_SAME or CTWS_LIFTED_DIFFERENT.
+ *     out   the pairs (u, v) with u < v, both labelled, hop distance 2 <= d(u, v) <= depth in the
+ *           whole graph (paths may run through unlabelled nodes and through ids below u; pairs
+ *           joined by an edge are not lifted), and labels that are equal (SAME), unequal
+ *           (DIFFERENT) or either (ALL) as uint64.  Rows (k x 2), ascending in (u, v): the order of
+ *           np.unique(axis=0).  A function of the inputs alone: repeated calls and host or device
+ *           pointers give the same bytes.
+ *   *n_out = k, always; CTWS_EINVAL when cap (in rows) is too small (nothing is written: retry with
+ *   *n_out rows), when a row holds an id >= n_nodes, has u >= v or is not above its predecessor,
+ *   for depth < 1 and for an unknown mode (the message says which).  n_edges == 0 and a labelling
+ *   without a labelled node give 0 rows without a launch.  Limits, CTWS_EUNSUPPORTED otherwise:
+ *   n_nodes < 2^32, n_edges < 2^31, k < 2^31.  Host pointers are staged through HBM; _device takes
+ *   device pointers on the handle's GPU for edges, node_labels and out.
+ */
+#define CTWS_LIFTED_ALL       0
+#define CTWS_LIFTED_SAME      1
+#define CTWS_LIFTED_DIFFERENT 2
+int ctws_lifted_neighborhood(ctws_handle* h, const uint64_t* edges, int64_t n_edges, const uint64_t* node_labels,
+                             int64_t n_nodes, int depth, int mode, uint64_t ignore_label, uint64_t* out, int64_t cap,
+                             int64_t* n_out);
+int ctws_lifted_neighborhood_device(ctws_handle* h, const uint64_t* edges, int64_t n_edges,
+                                    const uint64_t* node_labels, int64_t n_nodes, int depth, int mode,
+                                    uint64_t ignore_label, uint64_t* out, int64_t cap, int64_t* n_out);
+/* Two sizes of the search, for callers that size their tests by them (host code, no handle):
+ * *first_capacity = the keys the first pass has room for with n_sources labelled nodes (a graph
+ * with more lifted edges runs the search a second time at the counted size); *visited_capacity =
+ * the nodes a wave's on-chip visited set takes (a source that reaches more goes on in a bitmap). */
+int ctws_lifted_limits(int64_t n_sources, int64_t* first_capacity, int64_t* visited_capacity);
+
+/*
  * ThresholdedComponentsWorkflow, BlockComponents (thresholded_components/block_components.py:
  * 143-230: `_cc_block` / `_cc_block_with_mask`, threshold + skimage.morphology.label) on the GPU.
  *
