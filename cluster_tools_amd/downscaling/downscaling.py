@@ -17,10 +17,7 @@ Two things are refused, never guessed:
 * a block whose reduced box is smaller than its output box: `downsample_shape` makes the output
   longer than ceil(n / f) for a factor >= 3 on an extent it does not divide; the reference dies
   there in the write, here the job raises a ValueError that names the block and both shapes."""
-import json
 import os
-import sys
-from concurrent import futures
 
 import numpy as np
 
@@ -188,10 +185,6 @@ class DownscalingLSF(DownscalingBase, LSFTask):
 # Implementation
 #
 
-def _device():
-    return int(os.environ.get('CTWS_DEVICE', os.environ.get('LOCAL_RANK', '0')))
-
-
 def block_boxes(blocking, block_id, factors, halo, in_shape):
     """The boxes of one block (downscaling.py:232-263): the input box (the outer block in output
     coordinates, times the factor, clipped to the input), the output box (the inner block), the
@@ -227,12 +220,10 @@ def run_downscaling_blocks(blocking, block_list, ds_in, ds_out, factors, halo, f
         boxes = block_boxes(blocking, block_id, factors, halo, in_shape)
         return boxes, ds_in[lead + boxes[0]]
 
-    with ctws.Handle(_device()) as h, futures.ThreadPoolExecutor(1) as io:
-        nxt = io.submit(read, block_list[0]) if block_list else None
-        for k, block_id in enumerate(block_list):
+    with ctws.Handle(fu.device()) as h, fu.read_ahead(read, block_list) as ahead:
+        for block_id, nxt in ahead:
             fu.log("start processing block %i" % block_id)
             (in_bb, out_bb, local_bb), x = nxt.result()
-            nxt = io.submit(read, block_list[k + 1]) if k + 1 < len(block_list) else None
             channels = x if with_channels else x[None]
             reduced = [h.downscale_block(c, factors, function) for c in channels]
             # the reference samples nothing when the whole box (every channel) is zero
@@ -246,10 +237,7 @@ def run_downscaling_blocks(blocking, block_list, ds_in, ds_out, factors, halo, f
 
 
 def downscaling(job_id, config_path):
-    fu.log("start processing job %i" % job_id)
-    fu.log("reading config from %s" % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.load_config(job_id, config_path)
     function = check_library(config.get('library', 'vigra'), config.get('library_kwargs'))
     scale_factor = config['scale_factor']
     factors = [scale_factor] * 3 if isinstance(scale_factor, int) else list(scale_factor)
@@ -266,7 +254,4 @@ def downscaling(job_id, config_path):
 
 
 if __name__ == '__main__':
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    downscaling(job_id, path)
+    fu.run_job(downscaling)

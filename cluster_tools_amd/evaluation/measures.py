@@ -12,8 +12,6 @@ GpuMeasures{Local,Slurm,LSF}, task_name 'gpu_measures'; config keys threads_per_
 """
 import json
 import os
-import sys
-from concurrent import futures
 
 from cluster_tools_amd import luigi_compat as luigi
 import cluster_tools_amd.utils.volume_utils as vu
@@ -68,28 +66,22 @@ class GpuMeasuresLSF(GpuMeasuresBase, LSFTask):
 
 def gpu_measures(job_id, config_path):
     from cluster_tools_amd import ctws
-    fu.log("start processing job %i" % job_id)
-    fu.log("reading config from %s" % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
-    device = int(os.environ.get('CTWS_DEVICE', os.environ.get('LOCAL_RANK', '0')))
+    config = fu.load_config(job_id, config_path)
     with vu.file_reader(config['seg_path'], 'r') as fs, vu.file_reader(config['gt_path'], 'r') as fg, \
-            ctws.Handle(device) as h, futures.ThreadPoolExecutor(1) as io:
+            ctws.Handle(fu.device()) as h:
         ds_seg, ds_gt = fs[config['seg_key']], fg[config['gt_key']]
         assert tuple(ds_seg.shape) == tuple(ds_gt.shape)
         blocking = Blocking([0, 0, 0], list(ds_seg.shape), list(config['block_shape']))
-        n_blocks = blocking.numberOfBlocks
 
         def read(bid):
             bb = vu.block_to_bb(blocking.getBlock(bid))
             return ds_seg[bb].astype('uint64'), ds_gt[bb].astype('uint64')
 
         h.eval_begin(config['label_capacity'], config['pair_capacity'])
-        nxt = io.submit(read, 0) if n_blocks else None
-        for bid in range(n_blocks):
-            seg, gt = nxt.result()
-            nxt = io.submit(read, bid + 1) if bid + 1 < n_blocks else None
-            h.eval_add(seg, gt, ignore_gt_zero=config['ignore_label'])
+        with fu.read_ahead(read, range(blocking.numberOfBlocks)) as ahead:
+            for _, nxt in ahead:
+                seg, gt = nxt.result()
+                h.eval_add(seg, gt, ignore_gt_zero=config['ignore_label'])
         res = h.eval_end()
     results = {k: res[k] for k in ('vi-split', 'vi-merge', 'adapted-rand-error', 'rand-index')}
     with open(config['output_path'], 'w') as f:
@@ -98,7 +90,4 @@ def gpu_measures(job_id, config_path):
 
 
 if __name__ == '__main__':
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    gpu_measures(job_id, path)
+    fu.run_job(gpu_measures)

@@ -7,10 +7,7 @@ the box [block.begin, min(block.end + 1, shape)) through `Handle.edge_features_b
 sub-graph `s0/sub_graphs/block_<id>`, the table `blocks/block_<id>` (m, 10) written per block.
 The filter-response path (`filters`, `sigmas`) and the affinity path (`offsets`) are not built:
 a config that sets one of them is refused before any block is processed."""
-import json
 import os
-import sys
-from concurrent import futures
 
 from cluster_tools_amd import luigi_compat as luigi
 import cluster_tools_amd.utils.volume_utils as vu
@@ -93,10 +90,6 @@ def check_supported(config):
                                       "implemented on the GPU; only 3-D boundary maps are" % (key, what))
 
 
-def _device():
-    return int(os.environ.get('CTWS_DEVICE', os.environ.get('LOCAL_RANK', '0')))
-
-
 def run_feature_blocks(blocking, block_list, ds_in, ds_labels, f_graph, f_out):
     """The boundary-map accumulation for every block of the job."""
     from cluster_tools_amd import ctws
@@ -114,12 +107,10 @@ def run_feature_blocks(blocking, block_list, ds_in, ds_labels, f_graph, f_out):
         core = [int(e - b) for b, e in zip(block.begin, block.end)]
         return read_table(g, 'nodes'), edges, bool(g.attrs['ignoreLabel']), core, ds_labels[bb], ds_in[bb]
 
-    with ctws.Handle(_device()) as h, futures.ThreadPoolExecutor(1) as io:
-        nxt = io.submit(read, block_list[0]) if block_list else None
-        for k, block_id in enumerate(block_list):
+    with ctws.Handle(fu.device()) as h, fu.read_ahead(read, block_list) as ahead:
+        for block_id, nxt in ahead:
             fu.log("start processing block %i" % block_id)
             item = nxt.result()
-            nxt = io.submit(read, block_list[k + 1]) if k + 1 < len(block_list) else None
             if item is None:
                 fu.log("block %i has no edges" % block_id)
                 fu.log_block_success(block_id)
@@ -138,10 +129,7 @@ def run_feature_blocks(blocking, block_list, ds_in, ds_labels, f_graph, f_out):
 
 
 def block_edge_features(job_id, config_path):
-    fu.log("start processing job %i" % job_id)
-    fu.log("reading config from %s" % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.load_config(job_id, config_path)
     check_supported(config)
     graph_path = os.path.normpath(os.path.join(config['graph_block_prefix'], '..', '..', '..'))
     fu.log("accumulate features without applying filters")
@@ -160,7 +148,4 @@ def block_edge_features(job_id, config_path):
 
 
 if __name__ == '__main__':
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    block_edge_features(job_id, path)
+    fu.run_job(block_edge_features)

@@ -10,10 +10,7 @@ reference prefers fastfilters' approximations when that library is importable, w
 vigra's multi-channel filters are refused before any block is read: the reference's 3-D float32
 output dataset cannot hold them either.  A halo below a filter radius is legal, as in the
 reference: such blocks are computed with reflected borders, and the job says so once."""
-import json
 import os
-import sys
-from concurrent import futures
 
 from cluster_tools_amd import luigi_compat as luigi
 import cluster_tools_amd.utils.volume_utils as vu
@@ -116,10 +113,6 @@ def halo_warning(halo, filter_name, sigma, apply_in_2d=False):
             "their faces" % (list(halo), filter_name, sigma, ', '.join(short)))
 
 
-def _device():
-    return int(os.environ.get('CTWS_DEVICE', os.environ.get('LOCAL_RANK', '0')))
-
-
 def run_filter_blocks(blocking, block_list, ds_in, ds_out, halo, filter_name, sigma, apply_in_2d):
     """The filter response of every block of the job."""
     from cluster_tools_amd import ctws
@@ -128,12 +121,10 @@ def run_filter_blocks(blocking, block_list, ds_in, ds_out, halo, filter_name, si
         block = blocking.getBlockWithHalo(block_id, halo)
         return block, ds_in[vu.block_to_bb(block.outerBlock)]
 
-    with ctws.Handle(_device()) as h, futures.ThreadPoolExecutor(1) as io:
-        nxt = io.submit(read, block_list[0]) if block_list else None
-        for k, block_id in enumerate(block_list):
+    with ctws.Handle(fu.device()) as h, fu.read_ahead(read, block_list) as ahead:
+        for block_id, nxt in ahead:
             fu.log("start processing block %i" % block_id)
             block, data = nxt.result()
-            nxt = io.submit(read, block_list[k + 1]) if k + 1 < len(block_list) else None
             try:
                 response = h.image_filter(data, filter_name, sigma, apply_in_2d, normalize=True)
             except ctws.CtwsError as e:
@@ -143,10 +134,7 @@ def run_filter_blocks(blocking, block_list, ds_in, ds_out, halo, filter_name, si
 
 
 def image_filter(job_id, config_path):
-    fu.log("start processing job %i" % job_id)
-    fu.log("reading config from %s" % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.load_config(job_id, config_path)
     sigma, filter_name, halo = config['sigma'], config['filter_name'], config['halo']
     apply_in_2d = config.get('apply_in_2d', False)
     check_supported(filter_name, sigma, apply_in_2d)
@@ -165,7 +153,4 @@ def image_filter(job_id, config_path):
 
 
 if __name__ == '__main__':
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    image_filter(job_id, path)
+    fu.run_job(image_filter)

@@ -7,9 +7,7 @@ host with numpy over the blocks' `edgeIds`, as MapEdgeIds does.  Per global edge
 with that id and w = their count: count = sum w, mean and every quantile the w-weighted average,
 variance = sum w (var + (mean_r - mean)^2) / count, min / max over the rows with w > 0.  An edge
 without a row stays 0.  Restated (nifty is not available): DESIGN.md section 3.5."""
-import json
 import os
-import sys
 
 import numpy as np
 
@@ -114,10 +112,7 @@ def merge_feature_rows(ids, rows, edge_begin, edge_end):
 
 def merge_edge_features(job_id, config_path):
     from cluster_tools_amd.graph.serialization import read_table
-    fu.log("start processing job %i" % job_id)
-    fu.log("reading config from %s" % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.load_config(job_id, config_path)
     edge_block_list = config['block_list']
     assert (np.diff(edge_block_list) == 1).all(), "the edge chunks of a job are consecutive"
     n_edges, chunk = config['n_edges'], config['edge_chunk_size']
@@ -148,7 +143,4 @@ def merge_edge_features(job_id, config_path):
 
 
 if __name__ == '__main__':
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    merge_edge_features(job_id, path)
+    fu.run_job(merge_edge_features)

@@ -13,9 +13,7 @@ cast once to float32.  An id whose total count is 0 -- the ignore label, an id t
 -- gets 0; a row whose id is number_of_labels or more is an error.  The reference keeps a float32
 running average instead (:122-127); the two agree within float32 rounding.
 These are id tables, not voxels: vectorised numpy on the host."""
-import json
 import os
-import sys
 from itertools import product
 
 import numpy as np
@@ -111,10 +109,7 @@ def merge_rows(rows, node_begin, node_end):
 
 
 def merge_region_features(job_id, config_path):
-    fu.log("start processing job %i" % job_id)
-    fu.log("reading config from %s" % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.load_config(job_id, config_path)
     node_block_list = config['block_list']
     node_chunk_size = config['node_chunk_size']
     with vu.file_reader(config['output_path']) as f, vu.file_reader(config['tmp_path'], 'r') as f_in:
@@ -131,7 +126,4 @@ def merge_region_features(job_id, config_path):
 
 
 if __name__ == '__main__':
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    merge_region_features(job_id, path)
+    fu.run_job(merge_region_features)

@@ -9,10 +9,7 @@ dataset is float64, region_serialization.py).  The job replaces
 skip rule of `_block_features` holds: with an ignore label, a block that holds nothing else writes
 nothing.  A 4-D (multi-channel) input is the reference's own TODO and is refused before any job
 starts."""
-import json
 import os
-import sys
-from concurrent import futures
 
 import numpy as np
 
@@ -88,10 +85,6 @@ class RegionFeaturesLSF(RegionFeaturesBase, LSFTask):
 # Implementation
 #
 
-def _device():
-    return int(os.environ.get('CTWS_DEVICE', os.environ.get('LOCAL_RANK', '0')))
-
-
 def run_region_feature_blocks(blocking, block_list, ds_in, ds_labels, ds_out, ignore_label):
     """The [id, count, mean] table of every block of the job."""
     from cluster_tools_amd import ctws
@@ -101,27 +94,21 @@ def run_region_feature_blocks(blocking, block_list, ds_in, ds_labels, ds_out, ig
         bb = vu.block_to_bb(blocking.getBlock(block_id))
         return ds_labels[bb], ds_in[bb]
 
-    with ctws.Handle(_device()) as h, futures.ThreadPoolExecutor(1) as io:
-        nxt = io.submit(read, block_list[0]) if block_list else None
-        for k, block_id in enumerate(block_list):
+    with ctws.Handle(fu.device()) as h, fu.read_ahead(read, block_list) as ahead:
+        for block_id, nxt in ahead:
             fu.log("start processing block %i" % block_id)
             labels, data = nxt.result()
-            nxt = io.submit(read, block_list[k + 1]) if k + 1 < len(block_list) else None
             if ignore_label is not None and not (labels != ignore_label).any():
                 fu.log_block_success(block_id)
                 continue
-            block = blocking.getBlock(block_id)
-            chunk_id = tuple(int(beg // ch) for beg, ch in zip(block.begin, blocking.blockShape))
+            chunk_id = fu.chunk_id(blocking.getBlock(block_id), blocking)
             rows = h.region_features_block(np.ascontiguousarray(labels, dtype='uint64'), data, ignore_label)
             ds_out.write_chunk(chunk_id, serialize_region_features(rows), True)
             fu.log_block_success(block_id)
 
 
 def region_features(job_id, config_path):
-    fu.log("start processing job %i" % job_id)
-    fu.log("reading config from %s" % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.load_config(job_id, config_path)
     block_list = config['block_list']
     block_shape = config['block_shape']
     ignore_label = config['ignore_label']
@@ -135,7 +122,4 @@ def region_features(job_id, config_path):
 
 
 if __name__ == '__main__':
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    region_features(job_id, path)
+    fu.run_job(region_features)

@@ -5,10 +5,7 @@ block list / retry handling and log lines unchanged).  The job replaces the loop
 `ndist.computeMergeableRegionGraph(..., increaseRoi=True)` (:106-120): one library handle per job,
 blocks read ahead on a thread, the box [block.begin, min(block.end + 1, shape)) through
 `Handle.rag_block`, the group `s0/sub_graphs/block_<id>` written per block."""
-import json
 import os
-import sys
-from concurrent import futures
 
 from cluster_tools_amd import luigi_compat as luigi
 import cluster_tools_amd.utils.volume_utils as vu
@@ -73,10 +70,6 @@ class InitialSubGraphsLSF(InitialSubGraphsBase, LSFTask):
 # Implementation
 #
 
-def _device():
-    return int(os.environ.get('CTWS_DEVICE', os.environ.get('LOCAL_RANK', '0')))
-
-
 def extended_bb(block, shape):
     """increaseRoi=True: the one-voxel upper halo, so every edge across a block face lands in the
     lower block's sub-graph."""
@@ -93,12 +86,10 @@ def run_graph_blocks(blocking, block_list, ds, f_graph, ignore_label):
         bb = extended_bb(blocking.getBlock(block_id), shape)
         return bb, ds[bb]
 
-    with ctws.Handle(_device()) as h, futures.ThreadPoolExecutor(1) as io:
-        nxt = io.submit(read, block_list[0]) if block_list else None
-        for k, block_id in enumerate(block_list):
+    with ctws.Handle(fu.device()) as h, fu.read_ahead(read, block_list) as ahead:
+        for block_id, nxt in ahead:
             fu.log("start processing block %i" % block_id)
             bb, labels = nxt.result()
-            nxt = io.submit(read, block_list[k + 1]) if k + 1 < len(block_list) else None
             nodes, edges, _ = h.rag_block(labels, ignore_label)
             write_graph(f_graph, 's0/sub_graphs/block_%i' % block_id, nodes, edges, ignore_label,
                         roiBegin=[int(s.start) for s in bb], roiEnd=[int(s.stop) for s in bb])
@@ -106,10 +97,7 @@ def run_graph_blocks(blocking, block_list, ds, f_graph, ignore_label):
 
 
 def initial_sub_graphs(job_id, config_path):
-    fu.log("start processing job %i" % job_id)
-    fu.log("reading config from %s" % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.load_config(job_id, config_path)
     ignore_label = config.get('ignore_label', True)
     with vu.file_reader(config['input_path'], 'r') as f, vu.file_reader(config['graph_path']) as f_graph:
         ds = f[config['input_key']]
@@ -119,7 +107,4 @@ def initial_sub_graphs(job_id, config_path):
 
 
 if __name__ == '__main__':
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    initial_sub_graphs(job_id, path)
+    fu.run_job(initial_sub_graphs)

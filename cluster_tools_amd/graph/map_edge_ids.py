@@ -4,9 +4,7 @@ list, as the dataset `edgeIds` of the block's group (cluster_tools/graph/map_edg
 `ndist.mapEdgeIds` :94-113; parameters, config keys and log lines unchanged).  These are id
 tables, not voxels: one job on the host (ranks of the node ids + searchsorted), as
 SizeFilterBlocks merges its tables.  The dataset name is nifty's, recalled, not pinned."""
-import json
 import os
-import sys
 
 import numpy as np
 
@@ -96,10 +94,7 @@ class EdgeIndex:
 
 def map_edge_ids(job_id, config_path):
     from cluster_tools_amd.graph.serialization import read_table, write_edge_ids
-    fu.log("start processing job %i" % job_id)
-    fu.log("reading config from %s" % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.load_config(job_id, config_path)
     block_prefix = 's%i/sub_graphs/block_' % config['scale']
     with vu.file_reader(config['graph_path']) as f:
         index = EdgeIndex(read_table(f[config['input_key']], 'edges', 2))
@@ -110,7 +105,4 @@ def map_edge_ids(job_id, config_path):
 
 
 if __name__ == '__main__':
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    map_edge_ids(job_id, path)
+    fu.run_job(map_edge_ids)

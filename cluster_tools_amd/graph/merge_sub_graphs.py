@@ -10,9 +10,7 @@ other place uses `s%i/sub_graphs/block_` (n_scales > 1 cannot run as written); h
 the log `merge_sub_graphs_s<scale>_blocks.log`, the one that merges the complete graph
 `merge_sub_graphs_s<scale>.log`: with one name for both, the two tasks GraphWorkflow runs at
 scale n_scales - 1 would share their target."""
-import json
 import os
-import sys
 
 import numpy as np
 
@@ -80,10 +78,6 @@ class MergeSubGraphsLSF(MergeSubGraphsBase, LSFTask):
 # Implementation
 #
 
-def _device():
-    return int(os.environ.get('CTWS_DEVICE', os.environ.get('LOCAL_RANK', '0')))
-
-
 def merge_graphs(h, f, block_prefix, block_ids, output_key, **attrs):
     """The union of the groups block_prefix + id: sorted unique nodes, sorted unique edges."""
     from cluster_tools_amd.graph.serialization import read_graph, write_graph
@@ -104,14 +98,11 @@ def merge_graphs(h, f, block_prefix, block_ids, output_key, **attrs):
 
 def merge_sub_graphs(job_id, config_path):
     from cluster_tools_amd import ctws
-    fu.log("start processing job %i" % job_id)
-    fu.log("reading config from %s" % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.load_config(job_id, config_path)
     scale = config['scale']
     initial_block_shape = config['block_shape']
     block_list = config['block_list']
-    with vu.file_reader(config['graph_path']) as f, ctws.Handle(_device()) as h:
+    with vu.file_reader(config['graph_path']) as f, ctws.Handle(fu.device()) as h:
         shape = list(f.attrs['shape'])
         if config['merge_complete_graph']:
             fu.log("merge complete graph at scale %i" % scale)
@@ -139,7 +130,4 @@ def merge_sub_graphs(job_id, config_path):
 
 
 if __name__ == '__main__':
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    merge_sub_graphs(job_id, path)
+    fu.run_job(merge_sub_graphs)

@@ -5,9 +5,7 @@ keys, the one job without a prefix and log lines unchanged).  A lifted edge stay
 endpoints have equal labels in `node_labels`; the dataset is written again, with its chunks, only
 when rows were dropped.  If none stays there is nothing an n5 dataset could hold: the job raises
 and leaves the dataset as it was.  An id table: numpy on the host."""
-import json
 import os
-import sys
 
 from cluster_tools_amd import luigi_compat as luigi
 import cluster_tools_amd.utils.volume_utils as vu
@@ -64,10 +62,7 @@ def clear_edges(lifted_edges, node_labels):
 
 
 def clear_lifted_edges_from_labels(job_id, config_path):
-    fu.log("start processing job %i" % job_id)
-    fu.log("reading config from %s" % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.load_config(job_id, config_path)
     lifted_edge_key = config['lifted_edge_key']
     with vu.file_reader(config['node_labels_path'], 'r') as f:
         node_labels = f[config['node_labels_key']][:]
@@ -90,7 +85,4 @@ def clear_lifted_edges_from_labels(job_id, config_path):
 
 
 if __name__ == '__main__':
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    clear_lifted_edges_from_labels(job_id, path)
+    fu.run_job(clear_lifted_edges_from_labels)

@@ -6,9 +6,7 @@ min(262144, k) rows over the jobs and log lines unchanged).  Per lifted edge, fl
 intra_label_cost (6 by default, attractive) when the two labels are equal, inter_label_cost (-6,
 repulsive) otherwise; an endpoint with label 0 is an error, as the reference's assert (:131).
 These are id tables, not voxels: the job runs on the host with numpy, as MergeEdgeFeatures does."""
-import json
 import os
-import sys
 
 import numpy as np
 
@@ -108,10 +106,7 @@ def _costs_for_edge_block(block_id, blocking, ds_in, ds_out, node_labels, inter_
 
 
 def costs_from_node_labels(job_id, config_path):
-    fu.log("start processing job %i" % job_id)
-    fu.log("reading config from %s" % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.load_config(job_id, config_path)
     chunk_size = config['chunk_size']
     inter_label_cost, intra_label_cost = config['inter_label_cost'], config['intra_label_cost']
     with vu.file_reader(config['node_label_path'], 'r') as f:
@@ -128,7 +123,4 @@ def costs_from_node_labels(job_id, config_path):
 
 
 if __name__ == '__main__':
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    costs_from_node_labels(job_id, path)
+    fu.run_job(costs_from_node_labels)

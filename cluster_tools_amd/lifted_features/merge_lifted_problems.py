@@ -7,9 +7,7 @@ the reference (:121-125), the rows are NOT sorted again and an edge that two pro
 twice, each time with its own cost: a solver that wants it once sums them.  Chunks of
 min(k, 100000) rows.  `prefixs` is a list (the reference declares an IntParameter and hands it a
 list).  Id tables: numpy on the host."""
-import json
 import os
-import sys
 
 import numpy as np
 
@@ -66,10 +64,7 @@ class MergeLiftedProblemsLSF(MergeLiftedProblemsBase, LSFTask):
 #
 
 def merge_lifted_problems(job_id, config_path):
-    fu.log("start processing job %i" % job_id)
-    fu.log("reading config from %s" % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.load_config(job_id, config_path)
     out_prefix = config['out_prefix']
     with vu.file_reader(config['path']) as f:
         edges, costs = [], []
@@ -92,7 +87,4 @@ def merge_lifted_problems(job_id, config_path):
 
 
 if __name__ == '__main__':
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    merge_lifted_problems(job_id, path)
+    fu.run_job(merge_lifted_problems)

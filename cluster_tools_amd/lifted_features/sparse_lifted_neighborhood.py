@@ -8,9 +8,7 @@ apart that pass the mode test come back sorted and are written as (k, 2) uint64,
 (min(k, 262144), 2).  A graph without a lifted edge has no dataset to write (an n5 dataset has no
 zero extent, and the reference cannot represent it either): the job raises and writes nothing.
 Decided here (nifty is not available): DESIGN.md section 3.12."""
-import json
 import os
-import sys
 
 import numpy as np
 
@@ -81,10 +79,6 @@ class SparseLiftedNeighborhoodLSF(SparseLiftedNeighborhoodBase, LSFTask):
 # Implementation
 #
 
-def _device():
-    return int(os.environ.get('CTWS_DEVICE', os.environ.get('LOCAL_RANK', '0')))
-
-
 def write_lifted_edges(f, key, lifted):
     """The lifted edges as the dataset `key` of f; a table left by an earlier run is replaced."""
     lifted = np.ascontiguousarray(lifted, dtype='uint64').reshape(-1, 2)
@@ -98,10 +92,7 @@ def write_lifted_edges(f, key, lifted):
 def sparse_lifted_neighborhood(job_id, config_path):
     from cluster_tools_amd import ctws
     from cluster_tools_amd.graph.serialization import read_table
-    fu.log("start processing job %i" % job_id)
-    fu.log("reading config from %s" % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.load_config(job_id, config_path)
     graph_depth = config['nh_graph_depth']
     node_ignore_label = config['node_ignore_label']
     mode = config.get('mode', 'all')
@@ -112,7 +103,7 @@ def sparse_lifted_neighborhood(job_id, config_path):
     with vu.file_reader(config['node_label_path'], 'r') as f:
         node_labels = f[config['node_label_key']][:]
     fu.log("start lifted neighborhood extraction for depth %i" % graph_depth)
-    with ctws.Handle(_device()) as handle:
+    with ctws.Handle(fu.device()) as handle:
         lifted = handle.lifted_neighborhood(edges, node_labels, graph_depth, mode, node_ignore_label)
     if len(lifted) == 0:
         raise RuntimeError("sparse_lifted_neighborhood: no lifted edge for depth %i and mode %s (%i graph edges, "
@@ -128,7 +119,4 @@ def sparse_lifted_neighborhood(job_id, config_path):
 
 
 if __name__ == '__main__':
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    sparse_lifted_neighborhood(job_id, path)
+    fu.run_job(sparse_lifted_neighborhood)

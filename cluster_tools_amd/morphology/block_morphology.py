@@ -5,10 +5,7 @@ and log lines unchanged).  The job replaces `ndist.computeAndSerializeMorphology
 library handle per job, blocks read ahead on a thread, the rows of `Handle.block_morphology`
 written as one variable-length float64 chunk at the block's chunk id (serialization.py).  The skip
 rule of `_morphology_for_block` holds: a block whose labels sum to 0 writes nothing."""
-import json
 import os
-import sys
-from concurrent import futures
 
 import numpy as np
 
@@ -76,10 +73,6 @@ class BlockMorphologyLSF(BlockMorphologyBase, LSFTask):
 # Implementation
 #
 
-def _device():
-    return int(os.environ.get('CTWS_DEVICE', os.environ.get('LOCAL_RANK', '0')))
-
-
 def run_morphology_blocks(blocking, block_list, ds_in, ds_out):
     """The morphology table of every block of the job."""
     from cluster_tools_amd import ctws
@@ -88,28 +81,22 @@ def run_morphology_blocks(blocking, block_list, ds_in, ds_out):
     def read(block_id):
         return ds_in[vu.block_to_bb(blocking.getBlock(block_id))]
 
-    with ctws.Handle(_device()) as h, futures.ThreadPoolExecutor(1) as io:
-        nxt = io.submit(read, block_list[0]) if block_list else None
-        for k, block_id in enumerate(block_list):
+    with ctws.Handle(fu.device()) as h, fu.read_ahead(read, block_list) as ahead:
+        for block_id, nxt in ahead:
             fu.log("start processing block %i" % block_id)
             seg = nxt.result()
-            nxt = io.submit(read, block_list[k + 1]) if k + 1 < len(block_list) else None
             if seg.sum() == 0:
                 fu.log("block %i is empty" % block_id)
                 fu.log_block_success(block_id)
                 continue
             block = blocking.getBlock(block_id)
-            chunk_id = tuple(int(beg // ch) for beg, ch in zip(block.begin, blocking.blockShape))
             rows = h.block_morphology(np.ascontiguousarray(seg, dtype='uint64'), [int(b) for b in block.begin])
-            ds_out.write_chunk(chunk_id, serialize_morphology(rows), True)
+            ds_out.write_chunk(fu.chunk_id(block, blocking), serialize_morphology(rows), True)
             fu.log_block_success(block_id)
 
 
 def block_morphology(job_id, config_path):
-    fu.log("start processing job %i" % job_id)
-    fu.log("reading config from %s" % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.load_config(job_id, config_path)
     block_shape = config['block_shape']
     block_list = config['block_list']
     with vu.file_reader(config['input_path'], 'r') as f_in, vu.file_reader(config['output_path']) as f_out:
@@ -120,7 +107,4 @@ def block_morphology(job_id, config_path):
 
 
 if __name__ == '__main__':
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    block_morphology(job_id, path)
+    fu.run_job(block_morphology)

@@ -12,9 +12,7 @@ the block dataset in ascending block-id order and, for the ids of each of its la
 An id without a row gets eleven zeros; a row whose id is number_of_labels or more is an error.
 These are id tables, not voxels: vectorised numpy on the host.  Restated (nifty is not
 available): DESIGN.md section 3.7."""
-import json
 import os
-import sys
 from itertools import product
 
 import numpy as np
@@ -123,10 +121,7 @@ def merge_rows(rows, label_begin, label_end):
 
 
 def merge_morphology(job_id, config_path):
-    fu.log("start processing job %i" % job_id)
-    fu.log("reading config from %s" % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.load_config(job_id, config_path)
     block_list = config['block_list']
     out_shape, out_chunks = config['out_shape'], config['out_chunks']
     blocking = Blocking([0], list(out_shape[:1]), list(out_chunks[:1]))
@@ -141,7 +136,4 @@ def merge_morphology(job_id, config_path):
 
 
 if __name__ == '__main__':
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    merge_morphology(job_id, path)
+    fu.run_job(merge_morphology)

@@ -22,10 +22,7 @@ the larger boxes, transformed in 8 bytes per voxel of scratch, so the budget bou
 device memory of a job at about three times its value, and while one call runs the next one's
 crops are being read.  256 MiB holds the 2000 ids of a chunk in one call for typical fragments and
 is small beside a GPU's memory."""
-import json
 import os
-import sys
-from concurrent import futures
 
 import numpy as np
 
@@ -114,10 +111,6 @@ class RegionCentersLSF(RegionCentersBase, LSFTask):
 # Implementation
 #
 
-def _device():
-    return int(os.environ.get('CTWS_DEVICE', os.environ.get('LOCAL_RANK', '0')))
-
-
 def plan_calls(bb_start, bb_stop, label_begin, label_end, ignore_label, resolution, call_bytes=CALL_BYTES):
     """The ids of [label_begin, label_end) that have a non-empty box [bb_start, bb_stop), dealt to
     calls of at most call_bytes of labels: a list of lists of (label_id, begin, end).  An id whose
@@ -149,7 +142,7 @@ def plan_calls(bb_start, bb_stop, label_begin, label_end, ignore_label, resoluti
     return calls
 
 
-def region_centers_for_label_range(h, io, ds_in, ds_out, bb_start, bb_stop, label_begin, label_end, ignore_label,
+def region_centers_for_label_range(h, ds_in, ds_out, bb_start, bb_stop, label_begin, label_end, ignore_label,
                                    resolution):
     centers = np.zeros((label_end - label_begin, 3), dtype='float32')
     calls = plan_calls(bb_start, bb_stop, label_begin, label_end, ignore_label, resolution)
@@ -158,23 +151,19 @@ def region_centers_for_label_range(h, io, ds_in, ds_out, bb_start, bb_stop, labe
         return [np.ascontiguousarray(ds_in[tuple(slice(b, e) for b, e in zip(begin, end))], dtype='uint64')
                 for _, begin, end in call]
 
-    nxt = io.submit(read, calls[0]) if calls else None
-    for k, call in enumerate(calls):
-        crops = nxt.result()
-        nxt = io.submit(read, calls[k + 1]) if k + 1 < len(calls) else None
-        local, found = h.region_centers(crops, [label_id for label_id, _, _ in call], resolution)
-        for (label_id, begin, _), c, ok in zip(call, local, found):
-            if ok:  # (an object without a voxel in its box keeps its zero row)
-                centers[label_id - label_begin] = c + np.array(begin, dtype='int64')
+    with fu.read_ahead(read, calls) as ahead:
+        for call, nxt in ahead:
+            crops = nxt.result()
+            local, found = h.region_centers(crops, [label_id for label_id, _, _ in call], resolution)
+            for (label_id, begin, _), c, ok in zip(call, local, found):
+                if ok:  # (an object without a voxel in its box keeps its zero row)
+                    centers[label_id - label_begin] = c + np.array(begin, dtype='int64')
     ds_out[label_begin:label_end] = centers
 
 
 def region_centers(job_id, config_path):
     from cluster_tools_amd import ctws
-    fu.log("start processing job %i" % job_id)
-    fu.log("reading config from %s" % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.load_config(job_id, config_path)
     input_path, input_key = config['input_path'], config['input_key']
     ignore_label = config['ignore_label']
     resolution = integer_resolution(config['resolution'])
@@ -187,18 +176,15 @@ def region_centers(job_id, config_path):
     bb_start = morphology[:, 5:8].astype('uint64')
     bb_stop = morphology[:, 8:11].astype('uint64')
     with vu.file_reader(input_path, 'r') as f_in, vu.file_reader(config['output_path']) as f_out, \
-            ctws.Handle(_device()) as h, futures.ThreadPoolExecutor(1) as io:
+            ctws.Handle(fu.device()) as h:
         ds_in = f_in[input_key]
         ds_out = f_out[config['output_key']]
         for block_id in block_list:
             block = blocking.getBlock(block_id)
-            region_centers_for_label_range(h, io, ds_in, ds_out, bb_start, bb_stop, int(block.begin[0]),
+            region_centers_for_label_range(h, ds_in, ds_out, bb_start, bb_stop, int(block.begin[0]),
                                            int(block.end[0]), ignore_label, resolution)
     fu.log_job_success(job_id)
 
 
 if __name__ == '__main__':
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    region_centers(job_id, path)
+    fu.run_job(region_centers)

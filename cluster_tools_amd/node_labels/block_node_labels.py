@@ -6,10 +6,7 @@ one library handle per job, blocks read ahead on a thread, the rows of `Handle.l
 written as one variable-length chunk at the block's chunk id (serialization.py).  The two skip
 rules of `_labels_for_block` hold: a block whose fragments sum to 0 and, with an ignore label, a
 block whose labels are all that label write nothing."""
-import json
 import os
-import sys
-from concurrent import futures
 
 import numpy as np
 
@@ -88,10 +85,6 @@ class BlockNodeLabelsLSF(BlockNodeLabelsBase, LSFTask):
 # Implementation
 #
 
-def _device():
-    return int(os.environ.get('CTWS_DEVICE', os.environ.get('LOCAL_RANK', '0')))
-
-
 def run_label_blocks(blocking, block_list, ds_ws, labels, ds_out, ignore_label):
     """The overlaps of every block of the job."""
     from cluster_tools_amd import ctws
@@ -104,12 +97,10 @@ def run_label_blocks(blocking, block_list, ds_ws, labels, ds_out, ignore_label):
             return ws, None
         return ws, labels[bb].astype('uint64')
 
-    with ctws.Handle(_device()) as h, futures.ThreadPoolExecutor(1) as io:
-        nxt = io.submit(read, block_list[0]) if block_list else None
-        for k, block_id in enumerate(block_list):
+    with ctws.Handle(fu.device()) as h, fu.read_ahead(read, block_list) as ahead:
+        for block_id, nxt in ahead:
             fu.log("start processing block %i" % block_id)
             ws, labs = nxt.result()
-            nxt = io.submit(read, block_list[k + 1]) if k + 1 < len(block_list) else None
             if labs is None:
                 fu.log("block %i is empty" % block_id)
                 fu.log_block_success(block_id)
@@ -119,18 +110,14 @@ def run_label_blocks(blocking, block_list, ds_ws, labels, ds_out, ignore_label):
                 fu.log("labels of block %i is empty" % block_id)
                 fu.log_block_success(block_id)
                 continue
-            block = blocking.getBlock(block_id)
-            chunk_id = tuple(int(beg // ch) for beg, ch in zip(block.begin, blocking.blockShape))
+            chunk_id = fu.chunk_id(blocking.getBlock(block_id), blocking)
             rows = h.label_overlaps(np.ascontiguousarray(ws, dtype='uint64'), labs, ignore_label)
             ds_out.write_chunk(chunk_id, serialize_overlaps(rows), True)
             fu.log_block_success(block_id)
 
 
 def block_node_labels(job_id, config_path):
-    fu.log("start processing job %i" % job_id)
-    fu.log("reading config from %s" % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.load_config(job_id, config_path)
     block_shape = config['block_shape']
     block_list = config['block_list']
     ignore_label = config['ignore_label']
@@ -157,7 +144,4 @@ def block_node_labels(job_id, config_path):
 
 
 if __name__ == '__main__':
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    block_node_labels(job_id, path)
+    fu.run_job(block_node_labels)

@@ -14,9 +14,7 @@ block chunk, the counts of equal (node, label) rows are summed on the GPU
 
 max_overlap=True with serialize_counts=True has no form in the 1-D dataset and is refused before
 any job starts.  Restated (nifty is not available): DESIGN.md section 3.6."""
-import json
 import os
-import sys
 from itertools import product
 
 import numpy as np
@@ -103,10 +101,6 @@ class MergeNodeLabelsLSF(MergeNodeLabelsBase, LSFTask):
 # Implementation
 #
 
-def _device():
-    return int(os.environ.get('CTWS_DEVICE', os.environ.get('LOCAL_RANK', '0')))
-
-
 def max_overlap_labels(rows, label_begin, label_end, ignore_label):
     """out[node - label_begin] = the label of the largest count among the merged rows (m, 3) of the
     nodes [label_begin, label_end), the smallest label among tied ones; a node without a row gets
@@ -134,10 +128,7 @@ def read_block_rows(ds_in):
 def merge_node_labels(job_id, config_path):
     from cluster_tools_amd import ctws
     from cluster_tools_amd.node_labels.serialization import serialize_overlaps
-    fu.log("start processing job %i" % job_id)
-    fu.log("reading config from %s" % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.load_config(job_id, config_path)
     max_overlap, serialize_counts = config['max_overlap'], config['serialize_counts']
     check_supported(max_overlap, serialize_counts)
     ignore_label = config['ignore_label']
@@ -153,7 +144,7 @@ def merge_node_labels(job_id, config_path):
                 sel = rows[(rows[:, 0] >= np.uint64(label_begin)) & (rows[:, 0] < np.uint64(label_end))]
                 if len(sel):
                     if handle is None:
-                        handle = ctws.Handle(_device())
+                        handle = ctws.Handle(fu.device())
                     pairs, sums = handle.unique_pairs_u64(sel[:, :2], sel[:, 2])
                     sel = np.concatenate([pairs, sums[:, None]], axis=1)
                 if max_overlap:
@@ -167,7 +158,4 @@ def merge_node_labels(job_id, config_path):
 
 
 if __name__ == '__main__':
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    merge_node_labels(job_id, path)
+    fu.run_job(merge_node_labels)

@@ -5,10 +5,7 @@ lines unchanged).  `run_filter_blocks` is the job loop it shares with FillingSiz
 follows watershed_from_seeds.run_seeded_blocks: one library handle per job, the discard ids
 uploaded once, blocks in batches with a read-ahead thread, outputs written and "processed block"
 logged in block-list order."""
-import json
 import os
-import sys
-from concurrent import futures
 
 import numpy as np
 
@@ -78,10 +75,6 @@ def parse_discard_path(log_path):
     raise RuntimeError("Could not parse log file.")
 
 
-def _device():
-    return int(os.environ.get('CTWS_DEVICE', os.environ.get('LOCAL_RANK', '0')))
-
-
 def _read_block(blocking, block_id, ds_in, ds_hmap):
     bb = vu.block_to_bb(blocking.getBlock(block_id))
     b = {'block_id': block_id, 'bb': bb, 'labels': ds_in[bb]}
@@ -102,13 +95,11 @@ def run_filter_blocks(blocking, block_list, ds_in, ds_out, discard_ids, ds_hmap=
     def read_batch(ids):
         return [_read_block(blocking, bid, ds_in, ds_hmap) for bid in ids]
 
-    with ctws.Handle(_device()) as h, futures.ThreadPoolExecutor(1) as io:
+    # (in place the next batch is read while this one is written: other blocks, so no race)
+    with ctws.Handle(fu.device()) as h, fu.read_ahead(read_batch, batches) as ahead:
         h.set_discard_ids(discard_ids)
-        nxt = io.submit(read_batch, batches[0]) if batches else None
-        for bi in range(len(batches)):
+        for _, nxt in ahead:
             blocks = nxt.result()
-            # (in place the next batch is read while this one is written: other blocks, so no race)
-            nxt = io.submit(read_batch, batches[bi + 1]) if bi + 1 < len(batches) else None
             for b in blocks:
                 fu.log("start processing block %i" % b['block_id'])
             res = h.size_filter_blocks(blocks, fill=fill)
@@ -156,16 +147,10 @@ def run_filter_job(job_id, config, with_hmap):
 
 
 def background_size_filter(job_id, config_path):
-    fu.log("start processing job %i" % job_id)
-    fu.log("reading config from %s" % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.load_config(job_id, config_path)
     run_filter_job(job_id, config, with_hmap=False)
     fu.log_job_success(job_id)
 
 
 if __name__ == '__main__':
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    background_size_filter(job_id, path)
+    fu.run_job(background_size_filter)

@@ -8,9 +8,7 @@ The reference's job cannot run as written; this builds its evident intent (DESIG
 the uint64 labels are flooded as order-preserving compact ids and mapped back (vigra on
 labels.astype('uint32') wherever that cast is lossless), and 'maxId' is copied as
 BackgroundSizeFilter copies it."""
-import json
 import os
-import sys
 
 from cluster_tools_amd import luigi_compat as luigi
 import cluster_tools_amd.utils.volume_utils as vu
@@ -71,16 +69,10 @@ class FillingSizeFilterLSF(FillingSizeFilterBase, LSFTask):
 
 
 def filling_size_filter(job_id, config_path):
-    fu.log("start processing job %i" % job_id)
-    fu.log("reading config from %s" % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.load_config(job_id, config_path)
     run_filter_job(job_id, config, with_hmap=True)
     fu.log_job_success(job_id)
 
 
 if __name__ == '__main__':
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    filling_size_filter(job_id, path)
+    fu.run_job(filling_size_filter)

@@ -5,9 +5,7 @@ temp files unchanged).  One job merges the (unique, count) tables FindUniques(re
 wrote per job -- id tables, not voxels -- on the host with a sort and reduceat; the reference's
 dense `zeros(max_id + 1)` count array cannot hold un-relabelled watershed ids
 (block_id * prod(block_shape) + k)."""
-import json
 import os
-import sys
 
 import numpy as np
 
@@ -72,10 +70,7 @@ def merge_counts(unique_values, count_values):
 
 
 def size_filter_blocks(job_id, config_path):
-    fu.log("start processing job %i" % job_id)
-    fu.log("reading config from %s" % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.load_config(job_id, config_path)
     tmp_folder = config['tmp_folder']
     size_threshold = config['size_threshold']
     unique_values = [np.load(os.path.join(tmp_folder, 'find_uniques_job_%i.npy' % j)) for j in range(config['n_jobs'])]
@@ -92,7 +87,4 @@ def size_filter_blocks(job_id, config_path):
 
 
 if __name__ == '__main__':
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    size_filter_blocks(job_id, path)
+    fu.run_job(size_filter_blocks)

@@ -2,9 +2,7 @@
 """FindLabeling: consecutive new ids for the global uniques, as an (N, 2) uint64 assignment
 table (cluster_tools/relabel/find_labeling.py:20-126; task surface unchanged), merged on the
 GPU: 0 stays 0 if present, else ids start at 1."""
-import json
 import os
-import sys
 
 import numpy as np
 
@@ -60,15 +58,12 @@ def find_labeling(job_id, config_path):
     else at 1.  The (N, 2) uint64 table [old, new] is written to assignment_path/key.
     """
     from cluster_tools_amd import ctws
-    fu.log("start processing job %i" % job_id)
-    fu.log("reading config from %s" % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.load_config(job_id, config_path)
     tmp = config['tmp_folder']
     fu.log("read uniques")
     parts = [np.load(os.path.join(tmp, 'find_uniques_job_%i.npy' % j)) for j in range(config['n_jobs'])]
     fu.log("compute uniques")
-    with ctws.Handle(int(os.environ.get('CTWS_DEVICE', '0'))) as h:
+    with ctws.Handle(fu.device()) as h:
         old_ids = h.unique_u64(np.concatenate(parts))
     first = 0 if (len(old_ids) and old_ids[0] == 0) else 1
     n_ids = first + len(old_ids)
@@ -88,7 +83,4 @@ def find_labeling(job_id, config_path):
 
 
 if __name__ == '__main__':
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    find_labeling(job_id, path)
+    fu.run_job(find_labeling)

@@ -1,10 +1,7 @@
 #! /usr/bin/env python
 """FindUniques: per-job unique labels of the watershed output on the GPU
 (cluster_tools/relabel/find_uniques.py:20-159; task surface unchanged)."""
-import json
 import os
-import sys
-from concurrent import futures
 
 import numpy as np
 
@@ -53,10 +50,6 @@ class FindUniquesLSF(FindUniquesBase, LSFTask):
     pass
 
 
-def _device():
-    return int(os.environ.get('CTWS_DEVICE', os.environ.get('LOCAL_RANK', '0')))
-
-
 def find_uniques(job_id, config_path):
     """Job entry (find_uniques.py:115-159): the sorted unique ids of the job's blocks.
 
@@ -71,10 +64,7 @@ def find_uniques(job_id, config_path):
     handle and merges the sorted per-block sets with numpy.
     """
     from cluster_tools_amd import ctws
-    fu.log("start processing job %i" % job_id)
-    fu.log("reading config from %s" % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.load_config(job_id, config_path)
     return_counts = config['return_counts']
     block_list = config['block_list']
     cached = {}
@@ -96,8 +86,7 @@ def find_uniques(job_id, config_path):
         unique_values = np.unique(np.concatenate(per_block)) if per_block else np.zeros(0, 'uint64')
         _save(config, job_id, unique_values.astype('uint64'))
         return
-    with vu.file_reader(config['input_path'], 'r') as f, ctws.Handle(_device()) as h, \
-            futures.ThreadPoolExecutor(1) as io:
+    with vu.file_reader(config['input_path'], 'r') as f, ctws.Handle(fu.device()) as h:
         ds = f[config['input_key']]
         blocking = Blocking([0, 0, 0], list(ds.shape), list(config['block_shape']))
         to_read = [b for b in block_list if b not in cached]
@@ -106,27 +95,25 @@ def find_uniques(job_id, config_path):
             return ds[vu.block_to_bb(blocking.getBlock(block_id))]
 
         per_block, per_counts = [], []
-        nxt = io.submit(read, to_read[0]) if to_read else None
-        k = 0
-        for block_id in block_list:
-            fu.log("start processing block %i" % block_id)
-            if block_id in cached:
-                u = cached[block_id]
+        # the blocks that are read come from `ahead` in their order, between the cached ones
+        with fu.read_ahead(read, to_read) as ahead:
+            for block_id in block_list:
+                fu.log("start processing block %i" % block_id)
+                if block_id in cached:
+                    u = cached[block_id]
+                    per_block.append(u)
+                    if not (len(u) == 1 and u[0] == 0):
+                        fu.log_block_success(block_id)
+                    continue
+                labels = next(ahead)[1].result()
+                if return_counts:
+                    u, c = h.unique_counts_u64(labels)
+                    per_counts.append(c)
+                else:
+                    u = h.unique_u64(labels)
                 per_block.append(u)
                 if not (len(u) == 1 and u[0] == 0):
                     fu.log_block_success(block_id)
-                continue
-            labels = nxt.result()
-            k += 1
-            nxt = io.submit(read, to_read[k]) if k < len(to_read) else None
-            if return_counts:
-                u, c = h.unique_counts_u64(labels)
-                per_counts.append(c)
-            else:
-                u = h.unique_u64(labels)
-            per_block.append(u)
-            if not (len(u) == 1 and u[0] == 0):
-                fu.log_block_success(block_id)
         if return_counts and per_block:
             # counts of equal values summed over the blocks (find_uniques.py:143-151): a merge of
             # the per-block (value, count) tables -- uniques, not voxels -- on the host
@@ -151,7 +138,4 @@ def _save(config, job_id, unique_values):
 
 
 if __name__ == '__main__':
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    find_uniques(job_id, path)
+    fu.run_job(find_uniques)

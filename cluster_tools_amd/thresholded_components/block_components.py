@@ -11,11 +11,8 @@ numpy compares them with the Python float threshold, and the Gaussian prefilter
 (sigma_prefilter > 0, vigra gaussianSmoothing + normalize) runs on the GPU too
 (ctws_threshold_components_ex).
 """
-import contextlib
 import json
 import os
-import sys
-from concurrent import futures
 
 import numpy as np
 
@@ -115,10 +112,6 @@ class BlockComponentsLSF(BlockComponentsBase, LSFTask):
     pass
 
 
-def _device():
-    return int(os.environ.get('CTWS_DEVICE', os.environ.get('LOCAL_RANK', '0')))
-
-
 def _read_block(blocking, block_id, ds_in, mask, channel):
     """One block's input and mask (block_components.py:147-158 / :188-206): the unmasked single
     channel block is normalized on the GPU; channels are summed in the dataset dtype."""
@@ -158,50 +151,48 @@ def run_component_blocks(blocking, block_list, ds_in, ds_out, mask, config, keep
     offsets = {}
     # chunk inflate / deflate on a pool of the job's threads (libdeflate releases the GIL)
     ds_in.n_threads = ds_out.n_threads = max(1, int(config.get('threads_per_job', 1)))
-    with futures.ThreadPoolExecutor(1) as io, contextlib.ExitStack() as stack:
-        nxt = io.submit(_read_block, blocking, block_list[0], ds_in, mask, channel) if block_list else None
+
+    def read(block_id):
+        return _read_block(blocking, block_id, ds_in, mask, channel)
+
+    with fu.read_ahead(read, block_list) as ahead:
         if started is not None:
             started()
-        h = stack.enter_context(ctws.Handle(_device()))
-        for k, block_id in enumerate(block_list):
-            b = nxt.result()
-            nxt = (io.submit(_read_block, blocking, block_list[k + 1], ds_in, mask, channel)
-                   if k + 1 < len(block_list) else None)
-            fu.log("start processing block %i" % block_id)
-            if b.get('skip'):
-                offsets[block_id] = 0
+        with ctws.Handle(fu.device()) as h:
+            for block_id, nxt in ahead:
+                b = nxt.result()
+                fu.log("start processing block %i" % block_id)
+                if b.get('skip'):
+                    offsets[block_id] = 0
+                    if keep is not None:
+                        keep.append((block_id, b['bb'], None, 0))
+                    else:
+                        fu.log_block_success(block_id)
+                    continue
+                # normalized first: the unmasked single-channel block (`_cc_block`,
+                # block_components.py:150-151) and, before its prefilter, a masked block (:208-209);
+                # otherwise raw values (sigma 0) or the raw channel sum smoothed (:160-162)
+                prenorm = (mask is None and channel is None) or (mask is not None and sigma > 0)
+                labels, n = h.threshold_components(b['input'], threshold, mode, mask=b['mask'], normalize=prenorm,
+                                                   sigma=sigma)
+                offsets[block_id] = n + 1 if n else 0
                 if keep is not None:
-                    keep.append((block_id, b['bb'], None, 0))
-                else:
-                    fu.log_block_success(block_id)
-                continue
-            # normalized first: the unmasked single-channel block (`_cc_block`,
-            # block_components.py:150-151) and, before its prefilter, a masked block (:208-209);
-            # otherwise raw values (sigma 0) or the raw channel sum smoothed (:160-162)
-            prenorm = (mask is None and channel is None) or (mask is not None and sigma > 0)
-            labels, n = h.threshold_components(b['input'], threshold, mode, mask=b['mask'], normalize=prenorm,
-                                               sigma=sigma)
-            offsets[block_id] = n + 1 if n else 0
-            if keep is not None:
-                lab = None
-                if n and spill:
+                    lab = None
+                    if n and spill:
+                        ds_out[b['bb']] = labels
+                        lab = SpilledBlock(ds_out, b['bb'])
+                    elif n:
+                        lab = labels.astype(np.uint32)
+                    keep.append((block_id, b['bb'], lab, offsets[block_id]))
+                    continue
+                if n:
                     ds_out[b['bb']] = labels
-                    lab = SpilledBlock(ds_out, b['bb'])
-                elif n:
-                    lab = labels.astype(np.uint32)
-                keep.append((block_id, b['bb'], lab, offsets[block_id]))
-                continue
-            if n:
-                ds_out[b['bb']] = labels
-            fu.log_block_success(block_id)
+                fu.log_block_success(block_id)
     return offsets
 
 
 def block_components(job_id, config_path):
-    fu.log("start processing job %i" % job_id)
-    fu.log("reading config from %s" % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.load_config(job_id, config_path)
     fu.log("Applying threshold %f with mode %s" % (config['threshold'], config['threshold_mode']))
     channel = config.get('channel', None)
     with vu.file_reader(config['input_path'], 'r') as f_in, vu.file_reader(config['output_path']) as f_out:
@@ -256,7 +247,7 @@ def _run_blocks_merge(job_id, blocking, ds_in, ds_out, mask, config):
 
     def start_group():
         try:
-            job_relabel.init_group(job_id, m['n_jobs'], m['rendezvous'], m['backend'], device=_device())
+            job_relabel.init_group(job_id, m['n_jobs'], m['rendezvous'], m['backend'], device=fu.device())
         except Exception as e:  # recorded: a second rendezvous would only wait out the timeout again
             init_err.append(e)
             raise
@@ -280,7 +271,7 @@ def _run_blocks_merge(job_id, blocking, ds_in, ds_out, mask, config):
         if not group:   # (failed before its first read)
             start_group()
         merge_in_job(job_id, [] if failed else keep, blocking, block_list, owner, dict(m, tmp_folder=config['tmp_folder']),
-                     ds_out, log=fu.log, device=_device(), failed=failed is not None)
+                     ds_out, log=fu.log, device=fu.device(), failed=failed is not None)
     finally:
         if dist.is_initialized():
             dist.destroy_process_group()
@@ -289,7 +280,4 @@ def _run_blocks_merge(job_id, blocking, ds_in, ds_out, mask, config):
 
 
 if __name__ == '__main__':
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    block_components(job_id, path)
+    fu.run_job(block_components)

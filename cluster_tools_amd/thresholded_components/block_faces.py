@@ -10,7 +10,6 @@ components that meet only diagonally across a block face stay apart.
 """
 import json
 import os
-import sys
 
 import numpy as np
 
@@ -94,10 +93,7 @@ def _process_faces(block_id, blocking, ds, offsets, empty_blocks):
 
 
 def block_faces(job_id, config_path):
-    fu.log("start processing job %i" % job_id)
-    fu.log("reading config from %s" % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.load_config(job_id, config_path)
     with open(config['offsets_path']) as f:
         oc = json.load(f)
     offsets, empty_blocks, n_labels = oc['offsets'], set(oc['empty_blocks']), oc['n_labels']
@@ -116,7 +112,4 @@ def block_faces(job_id, config_path):
 
 
 if __name__ == '__main__':
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    block_faces(job_id, path)
+    fu.run_job(block_faces)

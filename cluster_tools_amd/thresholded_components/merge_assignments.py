@@ -11,7 +11,6 @@ consecutive.  Also as there: if any BlockFaces job found no pair, no pair is mer
 """
 import json
 import os
-import sys
 
 import numpy as np
 
@@ -61,10 +60,7 @@ class MergeAssignmentsLSF(MergeAssignmentsBase, LSFTask):
 
 def merge_assignments(job_id, config_path):
     from cluster_tools_amd import ctws
-    fu.log("start processing job %i" % job_id)
-    fu.log("reading config from %s" % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.load_config(job_id, config_path)
     with open(config['offset_path']) as f:
         n_labels = int(json.load(f)['n_labels'])
     parts = [np.load(os.path.join(config['tmp_folder'], '%s_%i.npy' % (config['save_prefix'], j)))
@@ -89,7 +85,4 @@ def merge_assignments(job_id, config_path):
 
 
 if __name__ == '__main__':
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    merge_assignments(job_id, path)
+    fu.run_job(merge_assignments)

@@ -4,7 +4,6 @@
 Writes {'offsets', 'empty_blocks', 'n_labels'} to save_path."""
 import json
 import os
-import sys
 
 import numpy as np
 
@@ -65,10 +64,7 @@ def scan_block_counts(counts):
 
 def merge_offsets(job_id, config_path):
     """Job entry (merge_offsets.py:83-131): the BlockComponents jobs' count files -> one scan."""
-    fu.log("start processing job %i" % job_id)
-    fu.log("reading config from %s" % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.load_config(job_id, config_path)
     counts = {}
     for j in range(config['n_jobs']):
         path = os.path.join(config['tmp_folder'], '%s_%i.json' % (config['save_prefix'], j))
@@ -88,7 +84,4 @@ def merge_offsets(job_id, config_path):
 
 
 if __name__ == '__main__':
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    merge_offsets(job_id, path)
+    fu.run_job(merge_offsets)

@@ -7,10 +7,10 @@ Both passes are libctws calls (cfg.pass_id); the checkerboard lists come from
 utils.volume_utils.make_checkerboard_block_lists (volume_utils.py:142-205).
 """
 import os
-import sys
 
 from cluster_tools_amd import luigi_compat as luigi
 import cluster_tools_amd.utils.volume_utils as vu
+import cluster_tools_amd.utils.function_utils as fu
 from cluster_tools_amd.utils.blocking import Blocking
 from cluster_tools_amd.cluster_tasks import SlurmTask, LocalTask, LSFTask
 from cluster_tools_amd.watershed.watershed import run_job, ws_task_setup
@@ -70,7 +70,4 @@ def two_pass_watershed(job_id, config_path):
 
 
 if __name__ == '__main__':
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    two_pass_watershed(job_id, path)
+    fu.run_job(two_pass_watershed)

@@ -10,10 +10,8 @@ keeps the dataset I/O, the outer/inner bounding boxes (_get_bbs, :252-264) and t
 writes of the previous one overlap the GPU work of the current batch.
 """
 import contextlib
-import json
 import os
 import shutil
-import sys
 from concurrent import futures
 
 import numpy as np
@@ -176,10 +174,6 @@ def _read_block(blocking, block_id, ds_in, ds_out, mask, config, pass_id, read_i
     return b
 
 
-def _device():
-    return int(os.environ.get('CTWS_DEVICE', os.environ.get('LOCAL_RANK', '0')))
-
-
 def _overlaps(a, b):
     return all(sa.start < sb.stop and sb.start < sa.stop for sa, sb in zip(a, b))
 
@@ -293,7 +287,7 @@ def run_blocks(blocking, block_list, ds_in, ds_out, mask, config, pass_id=0, bat
         nxt = io.submit(read_batch, batches[0]) if batches else None
         if started is not None:
             started()
-        h = stack.enter_context(ctws.Handle(_device()))
+        h = stack.enter_context(ctws.Handle(fu.device()))
         on_device = keep is not None and _keep_on_device(blocking, block_list, config)
         pending_write = None
         for bi in range(len(batches)):
@@ -358,7 +352,7 @@ def _keep_on_device(blocking, block_list, config):
         need += 8 * int(np.prod([s.stop - s.start for s in inner_bb]))
     n_jobs = int((config.get('relabel') or {}).get('n_jobs', 1))
     share = max(1, -(-n_jobs // max(1, torch.cuda.device_count())))
-    free, _ = torch.cuda.mem_get_info(_device())
+    free, _ = torch.cuda.mem_get_info(fu.device())
     return need <= free // (2 * share)
 
 
@@ -366,7 +360,7 @@ def _ws_blocks_resident(h, lib_config, block_shape, todo):
     """Pass-0 blocks through ctws_ws_blocks_device: the inputs uploaded, the outputs left in HBM
     as int64 tensors (uint64 bits) -> [{'output': tensor, 'status', 'max_label', 'n_ids'}]."""
     import torch
-    dev = torch.device('cuda', _device())
+    dev = torch.device('cuda', fu.device())
     dblocks = []
     for b in todo:
         db = {'block_id': b['block_id'], 'inner_begin': b['inner_begin'], 'crop_relabel': b['crop_relabel'],
@@ -382,10 +376,7 @@ def _ws_blocks_resident(h, lib_config, block_shape, todo):
 def run_job(job_id, config_path, pass_id=None):
     """Job entry shared by the watershed tasks: the job's blocks through run_blocks, pass 0
     (`_ws_block`) unless the config's 'pass' says 1 (`_ws_pass2`)."""
-    fu.log("start processing job %i" % job_id)
-    fu.log("reading config from %s" % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.load_config(job_id, config_path)
     pass_id = config.get('pass', 0) if pass_id is None else pass_id
     shape = list(vu.get_shape(config['input_path'], config['input_key']))[-3:]
     blocking = Blocking([0, 0, 0], shape, list(config['block_shape']))
@@ -413,7 +404,7 @@ def _run_blocks_relabel(job_id, blocking, ds_in, ds_out, mask, config, rel):
 
     def start_group():
         try:
-            job_relabel.init_group(job_id, rel['n_jobs'], rel['rendezvous'], rel['backend'], device=_device())
+            job_relabel.init_group(job_id, rel['n_jobs'], rel['rendezvous'], rel['backend'], device=fu.device())
         except Exception as e:  # recorded: a second rendezvous would only wait out the timeout again
             init_err.append(e)
             raise
@@ -433,7 +424,7 @@ def _run_blocks_relabel(job_id, blocking, ds_in, ds_out, mask, config, rel):
         if not group:   # (run_blocks failed before its first read)
             start_group()
         if failed is None:
-            with ctws.Handle(_device()) as h:
+            with ctws.Handle(fu.device()) as h:
                 def mapper(lab, keys, vals):
                     if hasattr(lab, 'data_ptr'):   # resident in HBM: map there, then download
                         if len(keys):
@@ -443,10 +434,10 @@ def _run_blocks_relabel(job_id, blocking, ds_in, ds_out, mask, config, rel):
                         h.lookup_u64(lab, keys, vals)
                     return lab
                 job_relabel.relabel_in_job(job_id, keep, ds_out, rel['tmp_folder'], rel['assignment_path'],
-                                           rel['assignment_key'], mapper, log=fu.log, device=_device())
+                                           rel['assignment_key'], mapper, log=fu.log, device=fu.device())
         else:
             job_relabel.relabel_in_job(job_id, [], ds_out, rel['tmp_folder'], rel['assignment_path'],
-                                       rel['assignment_key'], None, failed=True, log=fu.log, device=_device())
+                                       rel['assignment_key'], None, failed=True, log=fu.log, device=fu.device())
     finally:
         import torch.distributed as dist
         if dist.is_initialized():
@@ -460,7 +451,4 @@ def watershed(job_id, config_path):
 
 
 if __name__ == '__main__':
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    watershed(job_id, path)
+    fu.run_job(watershed)

@@ -10,10 +10,7 @@ flood, the size filter, labels -> seed values, mask), reads of the next batch ov
 GPU work of the current one.  Like the reference job, the seeds are read from the OUTPUT file
 (`ds_seeds = f_out[seeds_key]`, :236); `seeds_path` only travels in the job config.
 """
-import json
 import os
-import sys
-from concurrent import futures
 
 from cluster_tools_amd import luigi_compat as luigi
 import cluster_tools_amd.utils.volume_utils as vu
@@ -86,10 +83,6 @@ class WatershedFromSeedsLSF(WatershedFromSeedsBase, LSFTask):
 # Implementation
 #
 
-def _device():
-    return int(os.environ.get('CTWS_DEVICE', os.environ.get('LOCAL_RANK', '0')))
-
-
 def _read_block(blocking, block_id, ds_in, ds_seeds, mask, config):
     """One block's inputs (watershed_from_seeds.py:125-140 and :150-155 / :172-184)."""
     bb = vu.block_to_bb(blocking.getBlock(block_id))
@@ -123,11 +116,9 @@ def run_seeded_blocks(blocking, block_list, ds_in, ds_seeds, ds_out, mask, confi
     def read_batch(ids):
         return [_read_block(blocking, bid, ds_in, ds_seeds, mask, config) for bid in ids]
 
-    with ctws.Handle(_device()) as h, futures.ThreadPoolExecutor(1) as io:
-        nxt = io.submit(read_batch, batches[0]) if batches else None
-        for bi in range(len(batches)):
+    with ctws.Handle(fu.device()) as h, fu.read_ahead(read_batch, batches) as ahead:
+        for _, nxt in ahead:
             blocks = nxt.result()
-            nxt = io.submit(read_batch, batches[bi + 1]) if bi + 1 < len(batches) else None
             for b in blocks:
                 fu.log("start processing block %i" % b['block_id'])
             todo = [b for b in blocks if not b.get('skip')]
@@ -144,10 +135,7 @@ def run_seeded_blocks(blocking, block_list, ds_in, ds_seeds, ds_out, mask, confi
 
 
 def watershed_from_seeds(job_id, config_path):
-    fu.log("start processing job %i" % job_id)
-    fu.log("reading config from %s" % config_path)
-    with open(config_path) as f:
-        config = json.load(f)
+    config = fu.load_config(job_id, config_path)
     shape = list(vu.get_shape(config['input_path'], config['input_key']))
     if len(shape) == 4:
         shape = shape[1:]
@@ -166,7 +154,4 @@ def watershed_from_seeds(job_id, config_path):
 
 
 if __name__ == '__main__':
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    watershed_from_seeds(job_id, path)
+    fu.run_job(watershed_from_seeds)

@@ -4,8 +4,6 @@
 (k_u64_lookup); the pickled-dict assignment form is not supported (no unpickling of data)."""
 import json
 import os
-import sys
-from concurrent import futures
 
 import numpy as np
 
@@ -130,7 +128,7 @@ def write(job_id, config_path):
         offsets, skip = oc['offsets'], set(oc['empty_blocks'])
     block_list = [b for b in config['block_list'] if b not in skip]
     with vu.file_reader(input_path) as f_in, vu.file_reader(output_path) as f_out, \
-            ctws.Handle(int(os.environ.get('CTWS_DEVICE', '0'))) as h, futures.ThreadPoolExecutor(1) as io:
+            ctws.Handle(fu.device()) as h:
         ds_in, ds_out = f_in[input_key], f_out[output_key]
         blocking = Blocking([0, 0, 0], list(ds_in.shape), list(config['block_shape']))
         h.set_table_u64(keys, values)
@@ -139,29 +137,25 @@ def write(job_id, config_path):
             bb = vu.block_to_bb(blocking.getBlock(block_id))
             return bb, np.ascontiguousarray(ds_in[bb], dtype='uint64')
 
-        nxt = io.submit(read, block_list[0]) if block_list else None
-        for k, block_id in enumerate(block_list):
-            fu.log("start processing block %i" % block_id)
-            bb, seg = nxt.result()
-            nxt = io.submit(read, block_list[k + 1]) if k + 1 < len(block_list) else None
-            nz = seg != 0
-            if not nz.any():
+        with fu.read_ahead(read, block_list) as ahead:
+            for block_id, nxt in ahead:
+                fu.log("start processing block %i" % block_id)
+                bb, seg = nxt.result()
+                nz = seg != 0
+                if not nz.any():
+                    fu.log_block_success(block_id)
+                    continue
+                if offsets is not None:
+                    seg[nz] += np.uint64(offsets[block_id])
+                missing = h.lookup_u64(seg)
+                if missing and (is_array or not allow_empty):
+                    raise KeyError("block %i: %i labels are not in the assignment table" % (block_id, missing))
+                ds_out[bb] = seg
                 fu.log_block_success(block_id)
-                continue
-            if offsets is not None:
-                seg[nz] += np.uint64(offsets[block_id])
-            missing = h.lookup_u64(seg)
-            if missing and (is_array or not allow_empty):
-                raise KeyError("block %i: %i labels are not in the assignment table" % (block_id, missing))
-            ds_out[bb] = seg
-            fu.log_block_success(block_id)
         if job_id == 0:
             ds_out.attrs['maxId'] = int(values.max()) if len(values) else 0
     fu.log_job_success(job_id)
 
 
 if __name__ == '__main__':
-    path = sys.argv[1]
-    assert os.path.exists(path), path
-    job_id = int(os.path.split(path)[1].split('.')[0].split('_')[-1])
-    write(job_id, path)
+    fu.run_job(write)
