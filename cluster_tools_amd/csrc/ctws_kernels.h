@@ -496,6 +496,29 @@ __global__ void k_lf_unpack(const uint64_t*, int64_t, int, uint64_t*);
 hipError_t lf_scan(void* tmp, size_t& bytes, const uint32_t* in, uint32_t* out, int64_t n, hipStream_t stream);
 hipError_t lf_sort(void* tmp, size_t& bytes, const uint64_t* keys_in, uint64_t* keys_out, int64_t n, int end_bit,
                    hipStream_t stream);
+// k_graphpost.hip (ConnectedComponentsWorkflow, SizeFilterAndGraphWatershedWorkflow: graph components
+// and the seeded graph watershed over an edge table)
+constexpr int kGpMaxIters = 34;  // rounds of a watershed, and pointer-jumping passes of a round: then an error
+// the words of the edge checks' counter block
+constexpr int kGpBadId = 0, kGpBadNan = 1;
+__global__ void k_gp_init(uint32_t*, uint32_t*, uint64_t);
+__global__ void k_gp_union(const uint64_t*, uint64_t, uint64_t, const uint64_t*, uint32_t*, unsigned long long*);
+__global__ void k_gp_compress(uint32_t*, uint64_t);
+__global__ void k_gp_cc_flag(const uint32_t*, const uint64_t*, uint64_t, uint32_t*);
+__global__ void k_gp_cc_write(const uint32_t*, const uint64_t*, const uint32_t*, uint64_t, uint64_t*);
+__global__ void k_gp_keys(const uint64_t*, const double*, uint64_t, uint64_t, uint64_t*, uint32_t*, unsigned long long*);
+__global__ void k_gp_sorted_ends(const uint64_t*, const uint32_t*, uint64_t, uint32_t*, uint32_t*);
+__global__ void k_gp_offer(uint32_t*, const uint32_t*, uint64_t, const uint32_t*, const uint64_t*, uint32_t*);
+__global__ void k_gp_hook(const uint32_t*, const uint32_t*, const uint32_t*, const uint64_t*, const uint32_t*, uint32_t*,
+                          uint64_t, unsigned long long*);
+__global__ void k_gp_jump(uint32_t*, uint32_t*, uint64_t, unsigned long long*);
+__global__ void k_gp_ws_write(const uint32_t*, const uint64_t*, uint64_t, uint64_t*);
+__global__ void k_gp_rl_keys(const uint64_t*, uint64_t, uint64_t*, uint32_t*, uint32_t*);
+__global__ void k_gp_rl_heads(const uint64_t*, const uint32_t*, uint64_t, uint32_t*);
+__global__ void k_gp_rl_write(const uint64_t*, const uint32_t*, const uint32_t*, uint64_t, uint64_t*);
+hipError_t gp_scan(void* tmp, size_t& bytes, const uint32_t* in, uint32_t* out, int64_t n, hipStream_t stream);
+hipError_t gp_sort(void* tmp, size_t& bytes, const uint64_t* keys_in, uint64_t* keys_out, const uint32_t* vals_in,
+                   uint32_t* vals_out, int64_t n, hipStream_t stream);
 
 // k_threshcc.hip (ThresholdedComponents: BlockComponents)
 struct TcParams {

@@ -98,6 +98,11 @@ def lib():
                 getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int,
                                            C.c_uint64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
             L.ctws_lifted_limits.argtypes = [C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+            for fn in ('ctws_graph_components', 'ctws_graph_components_device'):
+                getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
+            for fn in ('ctws_graph_watershed', 'ctws_graph_watershed_device'):
+                getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                           C.c_int, C.c_void_p]
             L.ctws_threshold_components.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                                     C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p,
                                                     C.POINTER(C.c_int64)]
@@ -128,7 +133,8 @@ EXPORTED_SYMBOLS = ('ctws_abi_version', 'ctws_open', 'ctws_close', 'ctws_last_er
                     'ctws_region_features_block', 'ctws_region_features_block_device', 'ctws_downscale_block',
                     'ctws_downscale_block_device', 'ctws_region_centers', 'ctws_region_centers_device',
                     'ctws_filter_taps', 'ctws_image_filter', 'ctws_image_filter_device', 'ctws_lifted_neighborhood',
-                    'ctws_lifted_neighborhood_device', 'ctws_lifted_limits')
+                    'ctws_lifted_neighborhood_device', 'ctws_lifted_limits', 'ctws_graph_components',
+                    'ctws_graph_components_device', 'ctws_graph_watershed', 'ctws_graph_watershed_device')
 
 
 def ufd_find(n_labels, pairs):
@@ -895,6 +901,79 @@ class Handle:
             return ret, n.value, out
         k, out = self._call_sized('ctws_lifted_neighborhood_device', (lifted_limits(n_sources)[0],), call)
         return out[:k]
+
+    # ---- graph postprocessing kernels (ConnectedComponentsWorkflow, SizeFilterAndGraphWatershedWorkflow) ----
+
+    def graph_components(self, edges, assignments):
+        """The components of a node labelling in a graph (include/ctws.h, ctws_graph_components):
+        edges (m, 2) uint64 holds node ids below n = len(assignments); two nodes are joined when an
+        edge connects them and both carry the same non-zero assignment.  -> (n,) uint64: 0 where the
+        assignment is 0, else the component's number, from 1 in the order of the components'
+        smallest node ids.  CtwsError for an id >= n."""
+        edges = np.ascontiguousarray(edges, dtype=np.uint64).reshape(-1, 2)
+        assignments = np.ascontiguousarray(assignments, dtype=np.uint64).ravel()
+        out = np.empty(assignments.size, dtype=np.uint64)
+        self._check(lib().ctws_graph_components(self._h, edges.ctypes.data if len(edges) else None, len(edges),
+                                                assignments.ctypes.data if out.size else None, out.size,
+                                                out.ctypes.data if out.size else None), 'ctws_graph_components')
+        return out
+
+    def graph_components_device(self, edges, assignments):
+        """graph_components on two uint64 / int64 torch tensors on this GPU; the result is an int64
+        tensor (uint64 bits) on the same device: nothing crosses PCIe."""
+        import torch
+        for t in (edges, assignments):
+            assert t.is_cuda and t.is_contiguous() and t.element_size() == 8 and not t.is_floating_point()
+        assert edges.numel() % 2 == 0, edges.shape
+        torch.cuda.current_stream(assignments.device).synchronize()
+        m, n = edges.numel() // 2, assignments.numel()
+        out = torch.empty(n, dtype=torch.int64, device=assignments.device)
+        self._check(lib().ctws_graph_components_device(self._h, edges.data_ptr() if m else None, m,
+                                                       assignments.data_ptr() if n else None, n,
+                                                       out.data_ptr() if n else None), 'ctws_graph_components_device')
+        return out
+
+    def graph_watershed(self, edges, weights, seeds, relabel=False):
+        """The seeded watershed on a graph (include/ctws.h, ctws_graph_watershed): edges (m, 2)
+        uint64 with node ids below n = len(seeds), weights (m,) float64 (float32 is taken as
+        float64), seeds (n,) uint64 with 0 for an unlabelled node.  -> (n,) uint64, the labels of
+        the sequential flood that pops the edge with the smallest (weight, row index); nodes that
+        no seed reaches keep 0.  relabel: renumbered by first appearance over the node index, from
+        1, zeros kept.  ValueError for a weight table of another length, CtwsError for an id >= n
+        or a NaN weight.  The rounds it took are in timings()['gw_rounds']."""
+        edges = np.ascontiguousarray(edges, dtype=np.uint64).reshape(-1, 2)
+        weights = np.ascontiguousarray(weights, dtype=np.float64).ravel()
+        seeds = np.ascontiguousarray(seeds, dtype=np.uint64).ravel()
+        if len(weights) != len(edges):
+            raise ValueError("graph watershed: %i weights for %i edges" % (len(weights), len(edges)))
+        out = np.empty(seeds.size, dtype=np.uint64)
+        m = len(edges)
+        self._check(lib().ctws_graph_watershed(self._h, edges.ctypes.data if m else None,
+                                               weights.ctypes.data if m else None, m,
+                                               seeds.ctypes.data if out.size else None, out.size, int(bool(relabel)),
+                                               out.ctypes.data if out.size else None), 'ctws_graph_watershed')
+        return out
+
+    def graph_watershed_device(self, edges, weights, seeds, relabel=False):
+        """graph_watershed on torch tensors on this GPU: edges and seeds uint64 / int64, weights
+        float64 or float32 (converted on the device); the result is an int64 tensor (uint64 bits)
+        on the same device."""
+        import torch
+        for t in (edges, seeds):
+            assert t.is_cuda and t.is_contiguous() and t.element_size() == 8 and not t.is_floating_point()
+        assert weights.is_cuda and weights.dtype in (torch.float32, torch.float64), weights.dtype
+        assert edges.numel() % 2 == 0, edges.shape
+        m, n = edges.numel() // 2, seeds.numel()
+        if weights.numel() != m:
+            raise ValueError("graph watershed: %i weights for %i edges" % (weights.numel(), m))
+        weights = weights.to(torch.float64).contiguous().view(-1)
+        torch.cuda.current_stream(seeds.device).synchronize()
+        out = torch.empty(n, dtype=torch.int64, device=seeds.device)
+        self._check(lib().ctws_graph_watershed_device(self._h, edges.data_ptr() if m else None,
+                                                      weights.data_ptr() if m else None, m,
+                                                      seeds.data_ptr() if n else None, n, int(bool(relabel)),
+                                                      out.data_ptr() if n else None), 'ctws_graph_watershed_device')
+        return out
 
     # ---- NodeLabelWorkflow kernels ---------------------------------------------------------
     # first capacity of label_overlaps in rows: a call that does not fit computes everything again

@@ -1,1 +1,2 @@
-from .postprocess_workflow import SizeFilterWorkflow  # noqa: F401
+from .postprocess_workflow import (SizeFilterWorkflow, ConnectedComponentsWorkflow,  # noqa: F401
+                                   SizeFilterAndGraphWatershedWorkflow)

@@ -582,6 +582,42 @@ int ctws_lifted_neighborhood_device(ctws_handle* h, const uint64_t* edges, int64
 int ctws_lifted_limits(int64_t n_sources, int64_t* first_capacity, int64_t* visited_capacity);
 
 /*
+ * ConnectedComponentsWorkflow and SizeFilterAndGraphWatershedWorkflow
+ * (postprocess/postprocess_workflow.py:296-427): the two graph algorithms of the postprocessing over
+ * the merged graph's edge table (graph_connected_components.py:104-121,
+ * `ndist.connectedComponentsFromNodes` + `relabelConsecutive`; graph_watershed_assignments.py:152-178,
+ * `nifty.graph.edgeWeightedWatershedsSegmentation`; decided here: DESIGN.md section 3.13).
+ *
+ * Both: edges (n_edges x 2) holds node ids below n_nodes (u != v; the order of the rows and of a
+ * row's ends is free), the node array and out have n_nodes entries.  CTWS_EINVAL, with nothing
+ * written to out, when a row holds an id >= n_nodes; CTWS_EUNSUPPORTED for n_nodes >= 2^32 or
+ * n_edges >= 2^32.  n_edges == 0 launches no kernel over edges.  Results are functions of the inputs
+ * alone: repeated calls and host or device pointers give the same bytes.  Host pointers are staged
+ * through HBM; _device takes device pointers on the handle's GPU for every array.
+ *
+ * ctws_graph_components / _device: two nodes are joined when an edge connects them and both carry the
+ *   same non-zero assignment.  out[i] = 0 where assignments[i] == 0, else 1 + the number of
+ *   components whose smallest node id is below that of i's component.
+ *
+ * ctws_graph_watershed / _device: weights (n_edges) are float64, NaN is refused (CTWS_EINVAL), -0.0
+ *   counts as 0.0; seeds[i] == 0 means unlabelled.  out is the result of the sequential flood: every
+ *   edge between a labelled and an unlabelled node is queued, the edge with the smallest (weight,
+ *   row index) is popped, and if exactly one end is unlabelled it takes the other's label and its
+ *   edges to unlabelled nodes are queued.  Nodes that no seed reaches keep 0.  With relabel != 0 the
+ *   result is renumbered by first appearance over the node index, from 1, zeros kept.  out must not
+ *   be the seed array.  Computed in rounds whose number is bounded by the library (34, more than
+ *   log2 of any admissible n_nodes); CTWS_EHIP if the bound is ever reached.
+ */
+int ctws_graph_components(ctws_handle* h, const uint64_t* edges, int64_t n_edges, const uint64_t* assignments,
+                          int64_t n_nodes, uint64_t* out);
+int ctws_graph_components_device(ctws_handle* h, const uint64_t* edges, int64_t n_edges, const uint64_t* assignments,
+                                 int64_t n_nodes, uint64_t* out);
+int ctws_graph_watershed(ctws_handle* h, const uint64_t* edges, const double* weights, int64_t n_edges,
+                         const uint64_t* seeds, int64_t n_nodes, int relabel, uint64_t* out);
+int ctws_graph_watershed_device(ctws_handle* h, const uint64_t* edges, const double* weights, int64_t n_edges,
+                                const uint64_t* seeds, int64_t n_nodes, int relabel, uint64_t* out);
+
+/*
  * ThresholdedComponentsWorkflow, BlockComponents (thresholded_components/block_components.py:
  * 143-230: `_cc_block` / `_cc_block_with_mask`, threshold + skimage.morphology.label) on the GPU.
  *
