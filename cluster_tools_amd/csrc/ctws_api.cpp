@@ -32,235 +32,16 @@
 #include <utility>
 #include <vector>
 
-#include "../../include/ctws.h"
-#include "ctws_kernels.h"
-#include "host_pool.h"
+#include "ctws_host.h"
 
 using namespace ctws;
 
 namespace {
 
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-};
-
-struct Workspace {
-    int64_t cap_vox = 0, cap_words = 0, cap_chunks = 0, cap_slices = 0, cap_tiles = 0, cap_blocks = 0;
-    float *fin = nullptr, *dt = nullptr, *A = nullptr, *Bf = nullptr, *sm = nullptr, *hm = nullptr;
-    uint8_t* cls = nullptr;
-    uint32_t *P = nullptr, *PF = nullptr, *lab = nullptr;
-    uint64_t* key = nullptr;
-    uint64_t* W = nullptr;
-    uint32_t *Wp = nullptr, *csum = nullptr;
-    uint32_t *smin = nullptr, *smax = nullptr, *sb = nullptr, *slmax = nullptr, *soff = nullptr, *surv = nullptr;
-    uint32_t *act0 = nullptr, *act1 = nullptr, *lines0 = nullptr, *lines1 = nullptr;
-    BlockDesc* desc = nullptr;
-    BlockStat* stat = nullptr;
-    uint32_t* counter = nullptr;
-    double* taps = nullptr;  // [6][128]
-    // pass 2 (two-pass watershed) relabel hash
-    int64_t cap_hash = 0;
-    uint64_t* hkey = nullptr;
-    uint32_t* hpos = nullptr;
-    uint32_t* p2err = nullptr;
-    // frontier bitmaps of the descent flood
-    int64_t cap_front = 0;
-    uint64_t *front0 = nullptr, *front1 = nullptr, *fopen = nullptr;
-    uint64_t* fplat = nullptr;   // plateau fill (k_plateau.hip): the plateau voxels
-    uint64_t* fseed = nullptr;   // seed CC members (the seed forest's parents are written for members only)
-    uint32_t* plev = nullptr;    // per block: the plateau height (0: none)
-    uint32_t* fflags = nullptr;
-    uint32_t *fchunk0 = nullptr, *fchunk1 = nullptr;  // per 64-word chunk: generation of its last change
-    uint32_t *wl0 = nullptr, *wl1 = nullptr, *qgen = nullptr;  // chunk worklists, queued generation
-    uint32_t* wlcnt = nullptr;  // worklist length per iteration
-    int64_t cap_fstat = 0;
-    uint32_t* fstat = nullptr;  // CTWS_TRACE statistics: open voxels, frontier visits per block
-    uint32_t* sfacc = nullptr;  // k_sf_plan's sums, 4 per block
-};
-
 constexpr int kCounterBytes = 4 * (4 + 4 * kStatSlots);  // flood flag + statistics slots
 constexpr int kFrontierBatch = 8;        // frontier iterations per host check
 constexpr int kFrontierWavesHost = 4;    // waves per workgroup of k_frontier (kFrontierWaves)
-constexpr int kFrontierMaxIters = 256;   // then the tile flood takes over
 constexpr int kFrontierMaxItersCap = 4096;  // CTWS_FRONTIER_ITERS upper bound (worklist counters)
-
-}  // namespace
-
-struct ctws_handle {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::string err;
-    Workspace ws;
-    uint32_t* h_counter = nullptr;  // pinned
-    double* h_taps = nullptr;       // pinned [6][128]
-    std::vector<std::pair<const char*, float>> timings;
-    std::vector<hipEvent_t> events;
-    hipEvent_t fev[2] = {nullptr, nullptr};
-    uint64_t flood_tiles = 0, flood_iters = 0, flood_lines = 0;
-    // host-pointer staging
-    DevBuf st_in, st_mask, st_init, st_out;
-    // host-pointer path: two slots of pinned host staging + device staging, copy streams
-    struct HostSlot {
-        void* pin_in = nullptr;  // inputs | masks | initial seeds of a batch, packed
-        size_t pin_in_bytes = 0;
-        void* pin_out = nullptr;  // uint64 outputs of a batch
-        size_t pin_out_bytes = 0;
-        DevBuf d_in, d_out;
-        hipEvent_t ev_h2d = nullptr, ev_comp = nullptr, ev_d2h = nullptr;
-        hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;  // CTWS_TRACE: the batch's upload, timed
-        std::vector<hipEvent_t> ev_blk;  // per block of the batch: its output downloaded
-    } hslot[2];
-    hipStream_t s_in = nullptr, s_out = nullptr;
-    // relabel (k_relabel.hip)
-    DevBuf rl_lab, rl_bits, rl_cnt, rl_offs, rl_out, rl_keys, rl_vals, rl_red;
-    DevBuf rl_sorted, rl_uniq, rl_counts, rl_tmp;  // sort-based unique
-    int64_t rl_ntable = 0;  // entries of the resident assignment table (rl_keys / rl_vals)
-    // EDT: counters (64 B) + columns queued for the lower-envelope pass (k_edt_col_fh)
-    DevBuf edt_fh;
-    DevBuf xface;  // crop CC: the tiles' x columns (CcArgs::xface)
-    DevBuf ptile;  // plateau CC: per-tile plateau flags (CcArgs::ptile)
-    DevBuf edt_scratch;  // k_edt_real_line: per-thread parabola stacks
-    // WatershedFromSeeds (k_seeded.hip): distinct seed values, sorted values, segment offsets, sort temp
-    DevBuf fs_vals, fs_sorted, fs_off, fs_tmp;
-    // SizeFilterWorkflow (k_sizefilter.hip): the resident discard set (sorted ids; a bitmap over
-    // [ids[0], ids[n - 1]] when that range is small), the blocks' descriptors, facts and seeds
-    // (labels with the discarded ids zeroed), host-pointer staging of labels / height maps / outputs
-    DevBuf sf_ids, sf_bits, sf_desc, sf_stat, sf_seeds, sf_lab, sf_hm, sf_out;
-    // GraphWorkflow (k_rag.hip): host-pointer staging of labels / pairs / weights, the sorted
-    // endpoint table, the emitted node ids, pairs and weights, keys (then the unique keys), sorted keys and
-    // weights, summed weights, unpacked edges, sort / reduce temp, counters (append, runs, missing)
-    DevBuf rg_lab, rg_tab, rg_nodes, rg_pairs, rg_w, rg_keys, rg_skeys, rg_sw, rg_sum, rg_out, rg_tmp, rg_red;
-    // EdgeFeaturesWorkflow (k_edgefeat.hip): host-pointer staging of labels / data / nodes / edges / rows,
-    // the edge keys, the sample keys and their sorted copy, sort temp, counters (append, missing, bad edges)
-    DevBuf ef_lab, ef_data, ef_nodes, ef_edges, ef_out, ef_ekeys, ef_keys, ef_skeys, ef_tmp, ef_red;
-    // NodeLabelWorkflow (k_overlaps.hip): host-pointer staging of the second label array (the
-    // fragments take rg_lab), the rows (m x 3); everything else is the graph path's
-    DevBuf ov_lab, ov_rows;
-    // MorphologyWorkflow (k_morph.hip): the rows (m x 11) of the host-pointer path; the labels,
-    // records and sort buffers are the graph path's
-    DevBuf mo_rows, mo_acc;  // + the per-id integer table of the segments split over several waves
-    // RegionFeaturesWorkflow (k_regfeat.hip): host-pointer staging of the input map and the rows
-    // (m x 3), the rows' run counts and their scan, the records' sums, the chunk table (n, sum);
-    // the labels, keys and sort buffers are the graph path's
-    DevBuf rf_data, rf_rows, rf_cnt, rf_off, rf_sums, rf_ctab;
-    // DownscalingWorkflow (k_downscale.hip): host-pointer staging of the block and its reduction,
-    // the any-nonzero flag table and its host copy
-    DevBuf ds_in, ds_out, ds_flag;
-    std::vector<uint32_t> ds_flags;
-    // RegionCentersWorkflow (k_regcenter.hip): host-pointer staging of the labels, the objects and
-    // the lists of the two paths, the keys, the centres and flags of a host caller, the two scratch
-    // arrays of the larger boxes
-    DevBuf rc_lab, rc_objs, rc_list, rc_keys, rc_cent, rc_found, rc_a, rc_b;
-    // ImageFilter (k_imgfilter.hip): host-pointer staging of the block and the response, the
-    // responses between the passes (two after the first pass, three after the second), the taps of
-    // the call (three axes x orders 0 and n) and the min / max words
-    DevBuf if_in, if_out, if_a, if_b, if_taps, if_mm;
-    // LiftedFeaturesFromNodeLabelsWorkflow (k_lifted.hip): host-pointer staging of the edges, the labels
-    // and the rows; the degrees (then the fill's cursors), the CSR rows and lists, the labelled
-    // nodes, the waves' queues and bitmaps, the keys and their sorted copy, scan / sort temp, counters
-    DevBuf lf_edges, lf_lab, lf_out, lf_deg, lf_row, lf_adj, lf_src, lf_queue, lf_bits, lf_keys, lf_skeys, lf_tmp, lf_red;
-    // graph components and graph watershed (k_graphpost.hip): host-pointer staging of the edges, the
-    // weights, the node array and the result; the parents and their second copy, the offers (also
-    // the flags of a numbering) and the scanned flags, the edges' ends in rank order, the sort's keys
-    // and indices with their sorted copies, scan / sort temp, counters
-    DevBuf gp_edges, gp_w, gp_in, gp_out, gp_parent, gp_next, gp_best, gp_num, gp_su, gp_sv, gp_keys, gp_skeys, gp_idx,
-        gp_sidx, gp_tmp, gp_red;
-    std::vector<double> if_taps_host;  // what if_taps holds: a job's calls share their taps
-    int64_t sf_n = 0;
-    uint64_t sf_lo = 1, sf_hi = 0;
-    bool sf_has_bits = false;
-    // ThresholdedComponents (k_threshcc.hip): forest, root bitmap, chunk counts / offsets, word
-    // offsets, min / max + any flag, host-pointer staging
-    DevBuf tc_P, tc_bits, tc_cnt, tc_offs, tc_woff, tc_red, tc_in, tc_mask, tc_out, tc_raw, tc_tmp, tc_taps;
-    // evaluation (k_eval.hip): gt / seg / pair hash tables with counts, state, sums, staging
-    DevBuf ev_ka, ev_ca, ev_kb, ev_cb, ev_kp, ev_cp, ev_state, ev_out, ev_stage;
-    int64_t ev_cap_a = 0, ev_cap_b = 0, ev_cap_p = 0;
-    // test hooks
-    int stop_after = 0;
-    int trace = 0;       // CTWS_TRACE=1: per-round flood statistics on stderr
-    int no_descent = 0;  // CTWS_NO_DESCENT=1: flood from the seeds alone (test hook)
-    int seed_tilecc = 0;  // CTWS_SEED_TILECC=1: the seed CC by tiles (else k_seed_members / k_seed_union2)
-    // CTWS_SEED_DENSE=1: k_seed_members / k_plateau_flag over every class byte instead of the walk
-    // over k_localmax's equal bitmap (k_seed_members_eq / k_plateau_flag_eq)
-    int seed_dense = 0;
-    int no_fallback = 0; // CTWS_NO_FALLBACK=1: keep a failed descent result (debugging)
-    // CTWS_FORCE_WIDE=1: every flood on the wide keys (k_flood, 32-bit d; tests).  wide_rerun:
-    // run_batch is re-running blocks whose packed flood reported a saturated d (dsat)
-    int force_wide = 0;
-    int wide_rerun = 0;
-    int sf_sparse = 1;  // CTWS_SF_SPARSE=0: the size filter's regrow initialisation scans every block
-    int fuse_hist = 1;  // CTWS_FUSE_HIST=0: the first flood's check and the label histogram as two kernels
-    int verify = 1;      // CTWS_VERIFY: 1 (default) check the flood fixpoint + fallback, 2 fail on a violation (tests), 0 off
-    int prep_lds = 0;    // CTWS_PREP_LDS=1: LDS row kernel for the x pass at every row length (tests)
-    int plateau_fill = 1;  // CTWS_PLATEAU_FILL=0: masked blocks' plateaus relaxed hop by hop (k_plateau.hip)
-    int output_tile = 1;   // CTWS_OUTPUT_TILE=0: cropped blocks through the word-tiled k_output
-    int gauss_w = 0;            // CTWS_GAUSS_W (8, 16, 32): x positions per sliding-window column tile
-    int gauss_yx = 1;           // CTWS_GAUSS_YX=0: separate y and x passes instead of the fused tile kernel
-    int words_per_wave = 32;    // CTWS_WORDS_PER_WAVE: words per wave of the word-tiled kernels
-    // CTWS_D2H_WGS: workgroups of a device-to-host copy kernel; 0 (default): hipMemcpyAsync on the
-    // SDMA engines.  r03 (uint32 downloads, config 3): the copy kernel's workgroups slowed the
-    // concurrent compute from 94 to 140 ms per step (host-resident 7.69 vs 6.08 Gvoxel/s)
-    int d2h_wgs = 0;
-    int pack_threads = 6;       // CTWS_PACK_THREADS: threads packing inputs into pinned staging
-    int unpack_threads = 9;     // CTWS_UNPACK_THREADS: threads widening downloads into the outputs
-    std::unique_ptr<ctws_host::WorkerPool> pack_pool, unpack_pool;
-    int h2d_mode = 0;           // CTWS_H2D_MODE: 0 a copy per block as packed, 1 one copy per batch, 2 pull kernel
-    int h2d_wgs = 64;           // CTWS_H2D_WGS: workgroups of the pull kernel (mode 2)
-    int host_ramp = 1;          // CTWS_HOST_RAMP=0: equal batches (no smaller first / last batches)
-    int host_batch_blocks = 0;  // CTWS_HOST_BATCH_BLOCKS: cap on blocks per host-path batch (0: voxel cap)
-    int64_t host_batch_voxels = (int64_t)256 << 20;  // CTWS_HOST_BATCH_VOXELS: smaller batches pipeline better
-    int edt_wz = 0;  // CTWS_EDT_WZ: the same for the z pass alone (3-D DT)
-    // CTWS_EDT_BITS=0: the x pass writes g2 per voxel for every batch (k_prep_edt_x_co / _reg and
-    // k_edt_col) instead of the records of k_edt_col_bits
-    int edt_bits = 1;
-    int edt_w = 0;  // CTWS_EDT_W (8, 16, 32, 64): x positions per EDT column tile (0: by line length)
-    // CTWS_FRONTIER_CHUNK2D / _3D "CWxCYxCZ": frontier chunk brick (words x rows x slices, 64 words).
-    // 3-D batches with a mask: 1x32x2 was their default until round 5 (a masked region is one
-    // flat plateau the flood crosses hop by hop, and wider bricks in y cut the launches: config 5
-    // 104 -> 72 ms before the plateau fill); with the plateau fill and the alternating sweep
-    // order 1x8x8 relaxes config 5 faster (39.6 -> 36.4 ms, 132 -> 101 launches per step)
-    int fchunk2[3] = {1, 64, 1};
-    int fchunk3[3] = {1, 8, 8};
-    int fchunk3_masked[3] = {1, 8, 8};
-    int fchunk3_env = 0;  // CTWS_FRONTIER_CHUNK3D given: used for every 3-D batch
-    int fc_cur[3] = {1, 64, 1};  // the brick of the current batch (run_batch)
-    int cur_max[3] = {0, 0, 0};  // largest outer block extents (Z, Y, X) of the current batch
-    // CTWS_FRONTIER_GRID: workgroups of k_frontier (chunks in flight / 4).  1024 rather than 2048:
-    // half the chunks in flight keep more of each chunk's lines in L2 between its local sweeps
-    // (r04: config 3 relaxation 20.3 -> 18.5 ms per step; 512: 23.0 ms, too few waves)
-    int frontier_grid = 1024;
-    int frontier_dir = 1;    // CTWS_FRONTIER_DIR: local sweeps queue only the neighbours a change may lower
-    int frontier_reps = 32;  // CTWS_FRONTIER_REPS: local sweeps per chunk and launch (r02 sweep: 4 -> 32 cut k_frontier 19%)
-    int frontier_max_iters = kFrontierMaxIters;  // CTWS_FRONTIER_ITERS: then the tile flood finishes
-    std::vector<BlockDesc> last_desc;
-    // pass 2 (2-D): per block of the next run_batch, the slice offsets of its previous run (empty:
-    // none); a block with a wrapped-id merge runs again until its offsets are self-consistent
-    std::vector<std::vector<uint32_t>> p2_hints;
-    DevBuf p2_hint_dev;
-    int p2_depth = 0;
-    std::vector<uint8_t> last_bare;  // run_batch: per block, an in-mask voxel got the bare offset
-};
-
-namespace {
-
-#define HIPCHK(expr)                                                                     \
-    do {                                                                                 \
-        hipError_t e_ = (expr);                                                          \
-        if (e_ != hipSuccess) {                                                          \
-            h->err = std::string(#expr) + ": " + hipGetErrorString(e_);                  \
-            return CTWS_EHIP;                                                            \
-        }                                                                                \
-    } while (0)
-
-#define LAUNCHCHK()                                                                      \
-    do {                                                                                 \
-        hipError_t e_ = hipGetLastError();                                               \
-        if (e_ != hipSuccess) {                                                          \
-            h->err = std::string("kernel launch: ") + hipGetErrorString(e_);             \
-            return CTWS_EHIP;                                                            \
-        }                                                                                \
-    } while (0)
 
 template <class T>
 int dev_alloc(ctws_handle* h, T*& p, int64_t n) {
@@ -275,19 +56,6 @@ int dev_alloc(ctws_handle* h, T*& p, int64_t n) {
         p = nullptr;
         return CTWS_ENOMEM;
     }
-    return CTWS_OK;
-}
-
-int grow(ctws_handle* h, DevBuf& b, size_t bytes) {
-    if (b.bytes >= bytes) return CTWS_OK;
-    if (b.p) hipFree(b.p);
-    b.p = nullptr;
-    b.bytes = 0;
-    if (hipMalloc(&b.p, std::max<size_t>(bytes, 16)) != hipSuccess) {
-        h->err = "hipMalloc staging failed (" + std::to_string(bytes) + " bytes)";
-        return CTWS_ENOMEM;
-    }
-    b.bytes = bytes;
     return CTWS_OK;
 }
 
@@ -374,28 +142,6 @@ int ensure_workspace(ctws_handle* h, int64_t vox, int64_t words, int64_t chunks,
     if (!w.taps) ALLOC(taps, 6 * kTapSlot);
 #undef ALLOC
     return CTWS_OK;
-}
-
-// vigra Kernel1D<double>::initGaussian(sigma, 1.0) (restated; taps for offsets -r..r)
-std::vector<double> gaussian_taps(double sigma) {
-    std::vector<double> k;
-    if (sigma > 0.0) {
-        const double sigma2 = -0.5 / sigma / sigma;
-        const double norm = 1.0 / (std::sqrt(2.0 * M_PI) * sigma);
-        int radius = (int)(3.0 * sigma + 0.5);
-        if (radius == 0) radius = 1;
-        for (double x = -(double)radius; x <= (double)radius; ++x) {
-            const double x2 = x * x;
-            k.push_back(norm * std::exp(x2 * sigma2));
-        }
-    } else {
-        k.push_back(1.0);
-    }
-    double sum = 0.0;
-    for (double v : k) sum += v;
-    sum = 1.0 / sum;
-    for (double& v : k) v = v * sum;
-    return k;
 }
 
 struct BlockIO {
@@ -502,15 +248,6 @@ constexpr int kMaxColLen = (int)((kMaxLds - 1024) / 32);  // 5088
 // of LDS (config 4/5 z pass, 80-deep lines: 14.9 -> 13.8 / 14.3 -> 12.7 ms of EDT per step);
 // 16 up to 1024-long lines (a 576-long y line at 32 wide, 74 KiB, measured 9.1 vs 5.6 ms)
 int edt_col_width(int L) { return L <= 256 ? 32 : L <= 1024 ? 16 : 8; }
-
-void record(ctws_handle* h, size_t idx) {
-    while (h->events.size() <= idx) {
-        hipEvent_t e;
-        hipEventCreate(&e);
-        h->events.push_back(e);
-    }
-    hipEventRecord(h->events[idx], h->stream);
-}
 
 // ---- Gaussian passes over the active axes, z -> y -> x --------------------------------------
 #define CTWS_R12(M) M(1), M(2), M(3), M(4), M(5), M(6), M(7), M(8), M(9), M(10), M(11), M(12)
@@ -827,32 +564,8 @@ int run_frontier(ctws_handle* h, const Plan& pl, int nb, int64_t TF, int max_til
     return CTWS_OK;
 }
 
-
-
-void add_timing(ctws_handle* h, const char* name, float v);
-
 int64_t words_of(int64_t n) { return n / 64 + 1; }
 int64_t chunks_of(int64_t n) { return (words_of(n) + 255) / 256; }
-
-// timings of one ctws_ws_blocks call: summed over its batches (counts too)
-void add_timing(ctws_handle* h, const char* name, float v) {
-    for (auto& t : h->timings)
-        if (std::strcmp(t.first, name) == 0) {
-            t.second += v;
-            return;
-        }
-    h->timings.push_back({name, v});
-}
-
-// an entry that names something of the last batch (prep_kernel): replaced, not summed
-void set_timing(ctws_handle* h, const char* name, float v) {
-    for (auto& t : h->timings)
-        if (std::strcmp(t.first, name) == 0) {
-            t.second = v;
-            return;
-        }
-    h->timings.push_back({name, v});
-}
 
 // ---- WatershedFromSeeds seeds (k_seeded.hip) ----------------------------------------------
 // The blocks' distinct seed values (hash), sorted per block (segmented radix sort), a label
@@ -2137,17 +1850,6 @@ void pool_copy(ctws_host::WorkerPool& pool, const std::vector<std::pair<void*, c
     });
 }
 
-// host <-> device copy in pieces of at most 1 GiB: larger copies are not given to the SDMA
-// engines but run as a blit kernel that competes with the compute kernels for the CUs
-hipError_t copy_pieces(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {
-    constexpr size_t kPiece = (size_t)1 << 30;
-    for (size_t o = 0; o < bytes; o += kPiece) {
-        const hipError_t e = hipMemcpyAsync((char*)dst + o, (const char*)src + o, std::min(kPiece, bytes - o), kind, s);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
 int grow_pinned(ctws_handle* h, void*& p, size_t& have, size_t bytes) {
     if (have >= bytes) return CTWS_OK;
     if (p) hipHostFree(p);
@@ -2642,29 +2344,11 @@ void ctws_close(ctws_handle* h) {
     hipSetDevice(h->device);
     hipStreamSynchronize(h->stream);
     Workspace& w = h->ws;
+    // the DevBufs of the handle and of its slots free themselves in `delete h` below
     void* ptrs[] = {w.fin, w.dt, w.A, w.Bf, w.sm, w.hm, w.cls, w.P, w.PF, w.lab, w.key, w.W, w.Wp, w.csum,
                     w.smin, w.smax, w.sb, w.slmax, w.soff, w.surv, w.act0, w.act1, w.lines0, w.lines1, w.desc, w.stat, w.counter,
                     w.taps, w.hkey, w.hpos, w.p2err, w.front0, w.front1, w.fopen, w.fflags, w.fchunk0, w.fchunk1, w.wl0, w.wl1, w.qgen, w.wlcnt,
-                    w.fstat, w.sfacc, h->st_in.p, h->st_mask.p, h->st_init.p, h->st_out.p, h->rl_lab.p, h->rl_bits.p,
-                    h->rl_cnt.p, h->rl_offs.p, h->rl_out.p, h->rl_keys.p, h->rl_vals.p, h->rl_red.p,
-                    h->edt_fh.p, h->edt_scratch.p, h->p2_hint_dev.p, h->rl_sorted.p, h->rl_uniq.p, h->rl_counts.p, h->rl_tmp.p,
-                    h->fs_vals.p, h->fs_sorted.p, h->fs_off.p, h->fs_tmp.p, h->sf_ids.p, h->sf_bits.p, h->sf_desc.p,
-                    h->sf_stat.p, h->sf_seeds.p, h->sf_lab.p, h->sf_hm.p, h->sf_out.p, h->ev_ka.p, h->ev_ca.p, h->ev_kb.p,
-                    h->ev_cb.p, h->ev_kp.p, h->ev_cp.p, h->ev_state.p, h->ev_out.p, h->ev_stage.p,
-                    w.fplat, w.plev, w.fseed, h->tc_P.p, h->tc_bits.p, h->tc_cnt.p, h->tc_offs.p, h->tc_woff.p,
-                    h->tc_red.p, h->tc_in.p, h->tc_mask.p, h->tc_out.p, h->tc_raw.p, h->tc_tmp.p, h->tc_taps.p,
-                    h->rg_lab.p, h->rg_tab.p, h->rg_nodes.p, h->rg_pairs.p, h->rg_w.p, h->rg_keys.p, h->rg_skeys.p, h->rg_sw.p,
-                    h->rg_sum.p, h->rg_out.p, h->rg_tmp.p, h->rg_red.p, h->ef_lab.p, h->ef_data.p, h->ef_nodes.p,
-                    h->ef_edges.p, h->ef_out.p, h->ef_ekeys.p, h->ef_keys.p, h->ef_skeys.p, h->ef_tmp.p, h->ef_red.p,
-                    h->ov_lab.p, h->ov_rows.p, h->mo_rows.p, h->mo_acc.p, h->rf_data.p, h->rf_rows.p,
-                    h->rf_cnt.p, h->rf_off.p, h->rf_sums.p, h->rf_ctab.p, h->ds_in.p, h->ds_out.p,
-                    h->ds_flag.p, h->rc_lab.p, h->rc_objs.p, h->rc_list.p, h->rc_keys.p, h->rc_cent.p,
-                    h->rc_found.p, h->rc_a.p, h->rc_b.p, h->if_in.p, h->if_out.p, h->if_a.p, h->if_b.p,
-                    h->if_taps.p, h->if_mm.p, h->lf_edges.p, h->lf_lab.p, h->lf_out.p, h->lf_deg.p, h->lf_row.p,
-                    h->lf_adj.p, h->lf_src.p, h->lf_queue.p, h->lf_bits.p, h->lf_keys.p, h->lf_skeys.p, h->lf_tmp.p,
-                    h->lf_red.p, h->gp_edges.p, h->gp_w.p, h->gp_in.p, h->gp_out.p, h->gp_parent.p, h->gp_next.p,
-                    h->gp_best.p, h->gp_num.p, h->gp_su.p, h->gp_sv.p, h->gp_keys.p, h->gp_skeys.p, h->gp_idx.p,
-                    h->gp_sidx.p, h->gp_tmp.p, h->gp_red.p};
+                    w.fstat, w.sfacc, w.fplat, w.plev, w.fseed};
     for (void* p : ptrs)
         if (p) hipFree(p);
     for (auto e : h->events) hipEventDestroy(e);
@@ -2675,8 +2359,6 @@ void ctws_close(ctws_handle* h) {
     for (auto& sl : h->hslot) {
         if (sl.pin_in) hipHostFree(sl.pin_in);
         if (sl.pin_out) hipHostFree(sl.pin_out);
-        if (sl.d_in.p) hipFree(sl.d_in.p);
-        if (sl.d_out.p) hipFree(sl.d_out.p);
         for (hipEvent_t e : {sl.ev_h2d, sl.ev_comp, sl.ev_d2h, sl.ev_t0, sl.ev_t1})
             if (e) hipEventDestroy(e);
         for (hipEvent_t e : sl.ev_blk) hipEventDestroy(e);
@@ -2695,115 +2377,6 @@ int ctws_ws_blocks(ctws_handle* h, const ctws_cfg* cfg, ctws_block* blocks, int 
 
 int ctws_ws_blocks_device(ctws_handle* h, const ctws_cfg* cfg, ctws_block* blocks, int n_blocks) {
     return run_blocks(h, cfg, blocks, n_blocks, true);
-}
-
-// ---- evaluation: contingency table in HBM (k_eval.hip) ----------------------------------
-static int64_t pow2_at_least(int64_t v) {
-    int64_t c = 1024;
-    while (c < v) c <<= 1;
-    return c;
-}
-
-int ctws_eval_begin(ctws_handle* h, int64_t cap_labels, int64_t cap_pairs) {
-    if (!h || cap_labels < 0 || cap_pairs < 0) return CTWS_EINVAL;
-    h->err.clear();
-    HIPCHK(hipSetDevice(h->device));
-    const int64_t ca = pow2_at_least(2 * std::max<int64_t>(cap_labels, 1));
-    const int64_t cp = pow2_at_least(2 * std::max<int64_t>(cap_pairs, 1));
-    if (ca > (1ll << 31) || cp > (1ll << 33)) {  // slots + the 2^64 - 1 slot fit the pair key's 32-bit halves
-        h->err = "ctws_eval_begin: capacity too large";
-        return CTWS_EINVAL;
-    }
-    int r;
-    if ((r = grow(h, h->ev_ka, 8 * (size_t)(ca + 1))) != CTWS_OK || (r = grow(h, h->ev_ca, 8 * (size_t)(ca + 1))) != CTWS_OK ||
-        (r = grow(h, h->ev_kb, 8 * (size_t)(ca + 1))) != CTWS_OK || (r = grow(h, h->ev_cb, 8 * (size_t)(ca + 1))) != CTWS_OK ||
-        (r = grow(h, h->ev_kp, 8 * (size_t)cp)) != CTWS_OK || (r = grow(h, h->ev_cp, 8 * (size_t)cp)) != CTWS_OK ||
-        (r = grow(h, h->ev_state, 16)) != CTWS_OK || (r = grow(h, h->ev_out, 6 * sizeof(double))) != CTWS_OK)
-        return r;
-    h->ev_cap_a = h->ev_cap_b = ca;
-    h->ev_cap_p = cp;
-    HIPCHK(hipMemsetAsync(h->ev_ka.p, 0xFF, 8 * (size_t)(ca + 1), h->stream));
-    HIPCHK(hipMemsetAsync(h->ev_kb.p, 0xFF, 8 * (size_t)(ca + 1), h->stream));
-    HIPCHK(hipMemsetAsync(h->ev_kp.p, 0xFF, 8 * (size_t)cp, h->stream));
-    HIPCHK(hipMemsetAsync(h->ev_ca.p, 0, 8 * (size_t)(ca + 1), h->stream));
-    HIPCHK(hipMemsetAsync(h->ev_cb.p, 0, 8 * (size_t)(ca + 1), h->stream));
-    HIPCHK(hipMemsetAsync(h->ev_cp.p, 0, 8 * (size_t)cp, h->stream));
-    HIPCHK(hipMemsetAsync(h->ev_state.p, 0, 16, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return CTWS_OK;
-}
-
-int ctws_eval_add(ctws_handle* h, const uint64_t* seg, const uint64_t* gt, int64_t n, int on_device, int ignore_gt_zero) {
-    if (!h || n < 0 || (n > 0 && (!seg || !gt))) return CTWS_EINVAL;
-    if (!h->ev_cap_a) {
-        h->err = "ctws_eval_add before ctws_eval_begin";
-        return CTWS_EINVAL;
-    }
-    HIPCHK(hipSetDevice(h->device));
-    auto launch = [&](const uint64_t* s, const uint64_t* g, int64_t m) -> int {
-        const unsigned grid = (unsigned)std::min<int64_t>((m + 255) / 256, 8192);
-        k_eval_add<<<grid, 256, 0, h->stream>>>(s, g, m, ignore_gt_zero, (uint64_t*)h->ev_ka.p,
-                                                 (unsigned long long*)h->ev_ca.p, h->ev_cap_a, (uint64_t*)h->ev_kb.p,
-                                                 (unsigned long long*)h->ev_cb.p, h->ev_cap_b, (uint64_t*)h->ev_kp.p,
-                                                 (unsigned long long*)h->ev_cp.p, h->ev_cap_p,
-                                                 (unsigned long long*)h->ev_state.p);
-        LAUNCHCHK();
-        return CTWS_OK;
-    };
-    int r;
-    if (on_device) {
-        if ((r = launch(seg, gt, n)) != CTWS_OK) return r;
-    } else {
-        const int64_t chunk = (int64_t)1 << 25;  // voxels per staged piece (2 x 256 MiB)
-        if ((r = grow(h, h->ev_stage, 16 * (size_t)std::min(chunk, std::max<int64_t>(n, 1)))) != CTWS_OK) return r;
-        uint64_t* ds = (uint64_t*)h->ev_stage.p;
-        for (int64_t o = 0; o < n; o += chunk) {
-            const int64_t m = std::min(chunk, n - o);
-            uint64_t* dg = ds + std::min(chunk, std::max<int64_t>(n, 1));
-            HIPCHK(hipMemcpyAsync(ds, seg + o, 8 * (size_t)m, hipMemcpyHostToDevice, h->stream));
-            HIPCHK(hipMemcpyAsync(dg, gt + o, 8 * (size_t)m, hipMemcpyHostToDevice, h->stream));
-            if ((r = launch(ds, dg, m)) != CTWS_OK) return r;
-        }
-    }
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return CTWS_OK;
-}
-
-int ctws_eval_end(ctws_handle* h, double* scores, int64_t* n_points) {
-    if (!h || !scores) return CTWS_EINVAL;
-    if (!h->ev_cap_a) {
-        h->err = "ctws_eval_end before ctws_eval_begin";
-        return CTWS_EINVAL;
-    }
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipMemsetAsync(h->ev_out.p, 0, 6 * sizeof(double), h->stream));
-    const unsigned grid = (unsigned)std::min<int64_t>((std::max(h->ev_cap_a, h->ev_cap_p) + 255) / 256, 4096);
-    k_eval_reduce<<<grid, 256, 0, h->stream>>>((const uint64_t*)h->ev_ka.p, (const unsigned long long*)h->ev_ca.p,
-                                               h->ev_cap_a, (const uint64_t*)h->ev_kb.p,
-                                               (const unsigned long long*)h->ev_cb.p, h->ev_cap_b,
-                                               (const uint64_t*)h->ev_kp.p, (const unsigned long long*)h->ev_cp.p,
-                                               h->ev_cap_p, (const unsigned long long*)h->ev_state.p,
-                                               (double*)h->ev_out.p);
-    LAUNCHCHK();
-    double v[6];
-    unsigned long long st[2];
-    HIPCHK(hipMemcpyAsync(v, h->ev_out.p, sizeof(v), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(st, h->ev_state.p, sizeof(st), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (st[1]) {
-        h->err = "contingency hash table full: call ctws_eval_begin with larger capacities";
-        return CTWS_EUNSUPPORTED;
-    }
-    const double n = (double)st[0];
-    if (n_points) *n_points = (int64_t)st[0];
-    // validation_utils.py:60-76 (a = gt, b = seg) and :178-198
-    scores[0] = v[1] - v[2];  // vi split
-    scores[1] = v[0] - v[2];  // vi merge
-    const double prec = v[4] > 0 ? v[5] / v[4] : 0.0, rec = v[3] > 0 ? v[5] / v[3] : 0.0;
-    const double ari = (prec + rec) > 0 ? 2 * prec * rec / (prec + rec) : 0.0;
-    scores[2] = 1.0 - ari;
-    scores[3] = n > 0 ? 1.0 - (v[3] + v[4] - 2 * v[5]) / (n * n) : 1.0;
-    return CTWS_OK;
 }
 
 int ctws_ws_from_seeds(ctws_handle* h, const ctws_cfg* cfg, ctws_block* blocks, int n_blocks) {
@@ -3097,2290 +2670,6 @@ int ctws_debug_read(ctws_handle* h, const char* array, int block, void* dst, int
     }
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipMemcpy(dst, (const char*)src + d.base * es, (size_t)nbytes, hipMemcpyDeviceToHost));
-    return CTWS_OK;
-}
-
-}  // extern "C"
-
-namespace {
-// np.unique(labels[, return_counts]) by radix sort + run-length encoding (k_relabel.hip): any
-// value range.  dl: device labels; out / counts: caller buffers (device or host), cap entries.
-int unique_sorted(ctws_handle* h, const uint64_t* dl, int64_t n, int on_device, uint64_t* out, uint64_t* counts,
-                  int64_t cap, int64_t* n_unique) {
-    if (n >= (1ll << 31)) {
-        h->err = "unique: more than 2^31 - 1 labels in one call";
-        return CTWS_EUNSUPPORTED;
-    }
-    int r;
-    size_t tb_sort = 0, tb_rle = 0;
-    HIPCHK(u64_sort(nullptr, tb_sort, dl, nullptr, n, h->stream));
-    HIPCHK(u64_runs(nullptr, tb_rle, nullptr, nullptr, nullptr, nullptr, n, h->stream));
-    if ((r = grow(h, h->rl_sorted, sizeof(uint64_t) * (size_t)n)) != CTWS_OK) return r;
-    if ((r = grow(h, h->rl_uniq, sizeof(uint64_t) * (size_t)n)) != CTWS_OK) return r;
-    if ((r = grow(h, h->rl_counts, sizeof(uint64_t) * (size_t)n + 64)) != CTWS_OK) return r;
-    if ((r = grow(h, h->rl_tmp, std::max(tb_sort, tb_rle))) != CTWS_OK) return r;
-    uint64_t* sorted = (uint64_t*)h->rl_sorted.p;
-    uint64_t* uniq = (uint64_t*)h->rl_uniq.p;
-    uint64_t* cnt = (uint64_t*)h->rl_counts.p;
-    uint64_t* nruns = cnt + n;  // (the counts buffer has 64 spare bytes)
-    HIPCHK(u64_sort(h->rl_tmp.p, tb_sort, dl, sorted, n, h->stream));
-    HIPCHK(u64_runs(h->rl_tmp.p, tb_rle, sorted, uniq, cnt, nruns, n, h->stream));
-    uint64_t total = 0;
-    HIPCHK(hipMemcpyAsync(&total, nruns, sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    *n_unique = (int64_t)total;
-    if ((int64_t)total > cap) {
-        h->err = "unique: output capacity too small";
-        return CTWS_EINVAL;
-    }
-    const hipMemcpyKind k = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    if (total) {
-        HIPCHK(hipMemcpyAsync(out, uniq, sizeof(uint64_t) * total, k, h->stream));
-        if (counts) HIPCHK(hipMemcpyAsync(counts, cnt, sizeof(uint64_t) * total, k, h->stream));
-    }
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return CTWS_OK;
-}
-
-const uint64_t* stage_labels(ctws_handle* h, const uint64_t* labels, int64_t n, int on_device, int* r) {
-    *r = CTWS_OK;
-    if (on_device) return labels;
-    if ((*r = grow(h, h->rl_lab, sizeof(uint64_t) * (size_t)n)) != CTWS_OK) return nullptr;
-    if (hipMemcpyAsync(h->rl_lab.p, labels, sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice, h->stream) !=
-        hipSuccess) {
-        h->err = "unique: label upload failed";
-        *r = CTWS_EHIP;
-        return nullptr;
-    }
-    return (const uint64_t*)h->rl_lab.p;
-}
-}  // namespace
-
-extern "C" {
-
-// ---- RelabelWorkflow kernels (k_relabel.hip) ----------------------------------------------
-int ctws_unique_counts_u64(ctws_handle* h, const uint64_t* labels, int64_t n, int on_device, uint64_t* out,
-                           uint64_t* counts, int64_t cap, int64_t* n_unique) {
-    if (!h || (!labels && n > 0) || n < 0 || !n_unique || cap < 0 || ((!out || !counts) && cap > 0))
-        return CTWS_EINVAL;
-    h->err.clear();
-    HIPCHK(hipSetDevice(h->device));
-    *n_unique = 0;
-    if (n == 0) return CTWS_OK;
-    int r;
-    const uint64_t* dl = stage_labels(h, labels, n, on_device, &r);
-    if (r != CTWS_OK) return r;
-    return unique_sorted(h, dl, n, on_device, out, counts, cap, n_unique);
-}
-
-int ctws_unique_u64(ctws_handle* h, const uint64_t* labels, int64_t n, int on_device, uint64_t* out, int64_t cap,
-                    int64_t* n_unique) {
-    if (!h || (!labels && n > 0) || n < 0 || !n_unique || cap < 0 || (!out && cap > 0)) return CTWS_EINVAL;
-    h->err.clear();
-    HIPCHK(hipSetDevice(h->device));
-    *n_unique = 0;
-    if (n == 0) return CTWS_OK;
-    int r;
-    const uint64_t* dl = stage_labels(h, labels, n, on_device, &r);
-    if (r != CTWS_OK) return r;
-    if ((r = grow(h, h->rl_red, 4 * sizeof(uint64_t))) != CTWS_OK) return r;
-    unsigned long long* red = (unsigned long long*)h->rl_red.p;
-    const unsigned long long init[3] = {~0ull, 0ull, 0ull};
-    HIPCHK(hipMemcpyAsync(red, init, sizeof(init), hipMemcpyHostToDevice, h->stream));
-    const unsigned g = (unsigned)std::min<int64_t>((n + 255) / 256, 8192);
-    k_u64_range<<<g, 256, 0, h->stream>>>(dl, n, red);
-    LAUNCHCHK();
-    unsigned long long hr[3];
-    HIPCHK(hipMemcpyAsync(hr, red, sizeof(hr), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    const bool has_nz = hr[1] != 0ull;  // (the min stays ~0 when every nonzero label is 2^64 - 1)
-    const int64_t first = hr[2] ? 1 : 0;
-    int64_t total = first;
-    if (has_nz) {
-        const uint64_t lo = hr[0], span = hr[1] - hr[0];  // (+ 1 below; 0 .. 2^64 - 1 would wrap)
-        // the bitmap (span / 8 bytes) only while it is no larger than sorting the labels would
-        // need (~16 bytes each) or small anyway; otherwise sort (any value range)
-        if (span >= (1ull << 35) || span / 64 + 1 > (uint64_t)std::max<int64_t>(2 * n, 1 << 20))
-            return unique_sorted(h, dl, n, on_device, out, nullptr, cap, n_unique);
-        const int64_t nw = (int64_t)(span / 64 + 1), nc = (nw + 255) / 256;
-        if ((r = grow(h, h->rl_bits, sizeof(uint64_t) * (size_t)nw)) != CTWS_OK) return r;
-        if ((r = grow(h, h->rl_cnt, sizeof(uint32_t) * (size_t)nc)) != CTWS_OK) return r;
-        if ((r = grow(h, h->rl_offs, sizeof(uint64_t) * (size_t)(nc + 1))) != CTWS_OK) return r;
-        HIPCHK(hipMemsetAsync(h->rl_bits.p, 0, sizeof(uint64_t) * (size_t)nw, h->stream));
-        k_u64_bits<<<g, 256, 0, h->stream>>>(dl, n, lo, (unsigned long long*)h->rl_bits.p);
-        k_bits_chunk_count<<<(unsigned)nc, 256, 0, h->stream>>>((const uint64_t*)h->rl_bits.p, nw,
-                                                               (uint32_t*)h->rl_cnt.p);
-        k_scan_chunks<<<1, 256, 0, h->stream>>>((const uint32_t*)h->rl_cnt.p, nc, (uint64_t*)h->rl_offs.p);
-        LAUNCHCHK();
-        uint64_t cnt = 0;
-        HIPCHK(hipMemcpyAsync(&cnt, (uint64_t*)h->rl_offs.p + nc, sizeof(uint64_t), hipMemcpyDeviceToHost,
-                              h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        total += (int64_t)cnt;
-        *n_unique = total;
-        if (total > cap) {
-            h->err = "ctws_unique_u64: output capacity too small";
-            return CTWS_EINVAL;
-        }
-        uint64_t* dout = out;
-        if (!on_device) {
-            if ((r = grow(h, h->rl_out, sizeof(uint64_t) * (size_t)total)) != CTWS_OK) return r;
-            dout = (uint64_t*)h->rl_out.p;
-        }
-        k_bits_compact<<<(unsigned)nc, 256, 0, h->stream>>>((const uint64_t*)h->rl_bits.p, nw,
-                                                           (const uint64_t*)h->rl_offs.p, lo, (uint64_t)first, dout);
-        LAUNCHCHK();
-        if (first) HIPCHK(hipMemsetAsync(dout, 0, sizeof(uint64_t), h->stream));
-        if (!on_device)
-            HIPCHK(hipMemcpyAsync(out, dout, sizeof(uint64_t) * (size_t)total, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        return CTWS_OK;
-    }
-    *n_unique = total;  // only zeros
-    if (total > cap) {
-        h->err = "ctws_unique_u64: output capacity too small";
-        return CTWS_EINVAL;
-    }
-    if (on_device) HIPCHK(hipMemsetAsync(out, 0, sizeof(uint64_t), h->stream));
-    else out[0] = 0;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return CTWS_OK;
-}
-
-int ctws_set_table_u64(ctws_handle* h, const uint64_t* keys, const uint64_t* values, int64_t n_table) {
-    if (!h || n_table < 0 || ((!keys || !values) && n_table > 0)) return CTWS_EINVAL;
-    h->err.clear();
-    HIPCHK(hipSetDevice(h->device));
-    int r;
-    if ((r = grow(h, h->rl_keys, sizeof(uint64_t) * (size_t)std::max<int64_t>(1, n_table))) != CTWS_OK) return r;
-    if ((r = grow(h, h->rl_vals, sizeof(uint64_t) * (size_t)std::max<int64_t>(1, n_table))) != CTWS_OK) return r;
-    if (n_table) {
-        HIPCHK(hipMemcpyAsync(h->rl_keys.p, keys, sizeof(uint64_t) * (size_t)n_table, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(h->rl_vals.p, values, sizeof(uint64_t) * (size_t)n_table, hipMemcpyHostToDevice,
-                              h->stream));
-    }
-    HIPCHK(hipStreamSynchronize(h->stream));
-    h->rl_ntable = n_table;
-    return CTWS_OK;
-}
-
-int ctws_lookup_u64(ctws_handle* h, uint64_t* labels, int64_t n, int on_device, const uint64_t* keys,
-                    const uint64_t* values, int64_t n_table, int64_t* n_missing) {
-    if (!h || (!labels && n > 0) || n < 0) return CTWS_EINVAL;
-    const bool resident = !keys && !values;
-    if (!resident && (n_table < 0 || ((!keys || !values) && n_table > 0))) return CTWS_EINVAL;
-    h->err.clear();
-    HIPCHK(hipSetDevice(h->device));
-    if (n_missing) *n_missing = 0;
-    if (n == 0) return CTWS_OK;
-    int r;
-    if (resident) {
-        n_table = h->rl_ntable;
-    } else if (!on_device) {
-        // host table: upload it as the resident one
-        if ((r = ctws_set_table_u64(h, keys, values, n_table)) != CTWS_OK) return r;
-    }
-    const uint64_t* dk = (resident || !on_device) ? (const uint64_t*)h->rl_keys.p : keys;
-    const uint64_t* dv = (resident || !on_device) ? (const uint64_t*)h->rl_vals.p : values;
-    uint64_t* dl = labels;
-    if (!on_device) {
-        if ((r = grow(h, h->rl_lab, sizeof(uint64_t) * (size_t)n)) != CTWS_OK) return r;
-        dl = (uint64_t*)h->rl_lab.p;
-        HIPCHK(hipMemcpyAsync(dl, labels, sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-    }
-    if ((r = grow(h, h->rl_red, 4 * sizeof(uint64_t))) != CTWS_OK) return r;
-    unsigned long long* miss = (unsigned long long*)h->rl_red.p + 3;
-    HIPCHK(hipMemsetAsync(miss, 0, sizeof(uint64_t), h->stream));
-    const unsigned g = (unsigned)std::min<int64_t>((n + 255) / 256, 8192);
-    k_u64_lookup<<<g, 256, 0, h->stream>>>(dl, n, dk, dv, n_table, miss);
-    LAUNCHCHK();
-    unsigned long long hm = 0;
-    HIPCHK(hipMemcpyAsync(&hm, miss, sizeof(hm), hipMemcpyDeviceToHost, h->stream));
-    if (!on_device) HIPCHK(hipMemcpyAsync(labels, dl, sizeof(uint64_t) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (n_missing) *n_missing = (int64_t)hm;
-    return CTWS_OK;
-}
-
-// ---- the scaffold of the feature block calls below -------------------------------------------
-extern "C++" {
-namespace {
-// The words of a feature's counter block (rg_red; the edge features' own ef_red).  The appends of
-// all waves meet in an append counter, so each of the two has a 128-B line (16 words) to itself.
-enum RedWord : size_t {
-    kRedEmit = 0,       // the append counter of a counted emit
-    kRedPairRuns = 1,   // pairs_tail: the unique pairs ...
-    kRedPairMiss = 2,   // ... and the endpoint values missing from the id table
-    kRedNodes = 16,     // graph: the append counter of the node ids
-    kRedVmax = 16,      // morphology, region features: the largest id
-    kRedMissing = 16,   // edge features: the owned voxel pairs without an edge
-    kRedBadEdges = 17,  // edge features: edges not sorted, not unique or off the nodes
-    kRedRuns = 19,      // sort_by_id: the distinct ids
-    kRedWords = 32
-};
-
-// the stage between events a and b of this call, in ms
-void stage_time(ctws_handle* h, const char* name, size_t a, size_t b) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, h->events[a], h->events[b]) == hipSuccess) add_timing(h, name, ms);
-}
-
-int call_begin(ctws_handle* h) {
-    h->err.clear();
-    h->timings.clear();
-    HIPCHK(hipSetDevice(h->device));
-    return CTWS_OK;
-}
-
-// the kernels index a block with 32 bits: every extent and product of extents stays below 2^31
-int check_extent(ctws_handle* h, int64_t nz, int64_t ny, int64_t nx, const char* what, const char* unit,
-                 const char* why) {
-    constexpr int64_t kMax = 1ll << 31;
-    if (nz >= kMax || ny >= kMax || nx >= kMax || nz * ny >= kMax || nz * ny * nx >= kMax) {
-        h->err = std::string(what) + ": 2^31 or more voxels in one " + unit + " (" + why + ")";
-        return CTWS_EUNSUPPORTED;
-    }
-    return CTWS_OK;
-}
-
-// An input array of a call -> *d, the device pointer to read: the caller's own with dev, else its
-// copy in b.
-template <class T>
-int stage_in(ctws_handle* h, DevBuf& b, const T* src, size_t bytes, bool dev, const T** d) {
-    *d = src;
-    if (dev) return CTWS_OK;
-    const int r = grow(h, b, bytes);
-    if (r != CTWS_OK) return r;
-    HIPCHK(copy_pieces(b.p, src, bytes, hipMemcpyHostToDevice, h->stream));
-    *d = (const T*)b.p;
-    return CTWS_OK;
-}
-
-// A result array of a call.  out_begin -> *d, the device pointer to write: the caller's own with
-// dev, else b.  out_end ends the call: the download for a host caller, and the one wait.
-template <class T>
-int out_begin(ctws_handle* h, DevBuf& b, T* dst, size_t bytes, bool dev, T** d) {
-    *d = dst;
-    if (dev) return CTWS_OK;
-    const int r = grow(h, b, bytes);
-    *d = (T*)b.p;
-    return r;
-}
-
-int out_end(ctws_handle* h, void* dst, const void* d, size_t bytes, bool dev) {
-    if (!dev) HIPCHK(copy_pieces(dst, d, bytes, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return CTWS_OK;
-}
-
-// The counted emit.  A kernel appends records to buffers and counts every append, also those that
-// found no room.  First capacities that depend on the block alone (so a call behaves the same
-// whatever the handle ran before); the pass is repeated once at the counted sizes when one did
-// not fit.
-struct EmitCap {
-    RedWord word;            // the counter that ...
-    unsigned long long cap;  // ... this capacity bounds
-};
-struct Emitted {
-    unsigned long long w[kRedWords] = {0};  // the counters as read back
-    int passes = 0;
-};
-unsigned long long first_cap(int64_t n, int64_t div) { return (unsigned long long)std::max<int64_t>(64, n / div); }
-
-// cnt: the counter block; its first nzero words are zeroed before a pass and nread read back after
-// it.  launch() grows the record buffers to caps and launches; check(w) is the feature's own look
-// at the counters of a pass.
-template <class Launch, class Check>
-int counted_emit(ctws_handle* h, const char* what, unsigned long long* cnt, size_t nzero, size_t nread, EmitCap* caps,
-                 int ncaps, Launch launch, Check check, Emitted* e) {
-    int r, attempt = 0;
-    for (; attempt < 2; ++attempt) {
-        HIPCHK(hipMemsetAsync(cnt, 0, nzero * sizeof(uint64_t), h->stream));
-        if ((r = launch()) != CTWS_OK) return r;
-        LAUNCHCHK();
-        HIPCHK(hipMemcpyAsync(e->w, cnt, nread * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        if ((r = check(e->w)) != CTWS_OK) return r;
-        bool fit = true;
-        for (int c = 0; c < ncaps; ++c) fit = fit && e->w[caps[c].word] <= caps[c].cap;
-        if (fit) break;
-        if (attempt == 1) {
-            h->err = std::string(what) + ": the emit counts changed between two passes over the same input";
-            return CTWS_EHIP;
-        }
-        for (int c = 0; c < ncaps; ++c) caps[c].cap = std::max(caps[c].cap, e->w[caps[c].word]);
-    }
-    e->passes = attempt + 1;
-    return CTWS_OK;
-}
-
-// a check of counted_emit: at least lo runs and at most one per voxel, or no second pass helps
-int runs_within(ctws_handle* h, const char* what, unsigned long long runs, int64_t lo, int64_t n) {
-    if (runs >= (unsigned long long)lo && runs <= (unsigned long long)n) return CTWS_OK;
-    h->err = std::string(what) + ": the kernel counted " + std::to_string(runs) + " runs in " + std::to_string(n) +
-             " voxels";
-    return CTWS_EHIP;
-}
-
-// Sort by id and run-length encode: n (id, record) pairs on the device -> the pairs sorted by id
-// (rg_skeys, rg_sw) and the distinct ids with their numbers of pairs (rg_keys, rg_sum).  vmax: the
-// largest id, for the sort's bits; the ids become float64 columns, so 2^53 or more is refused.
-// ev: the event recorded behind the two launches.  The counters are those of rg_red.
-struct ById {
-    uint64_t *sids, *srecs, *uniq, *counts;
-    int64_t m;  // the distinct ids
-};
-int sort_by_id(ctws_handle* h, const char* what, const uint64_t* ids, const uint64_t* recs, int64_t n,
-               unsigned long long vmax, size_t ev, ById* o) {
-    if (vmax >= (1ull << 53)) {
-        h->err = std::string(what) + ": an id of 2^53 or more (" + std::to_string(vmax) +
-                 ") has no exact place in the float64 rows";
-        return CTWS_EUNSUPPORTED;
-    }
-    int bits = 1;
-    while (bits < 53 && (1ull << bits) <= vmax) ++bits;
-    int r;
-    const size_t nb = sizeof(uint64_t) * (size_t)n;
-    size_t tb_sort = 0, tb_rle = 0;
-    HIPCHK(pair_sort(nullptr, tb_sort, nullptr, nullptr, nullptr, nullptr, n, bits, h->stream));
-    HIPCHK(u64_runs(nullptr, tb_rle, nullptr, nullptr, nullptr, nullptr, n, h->stream));
-    if ((r = grow(h, h->rg_skeys, nb)) != CTWS_OK) return r;
-    if ((r = grow(h, h->rg_sw, nb)) != CTWS_OK) return r;
-    if ((r = grow(h, h->rg_keys, nb)) != CTWS_OK) return r;
-    if ((r = grow(h, h->rg_sum, nb)) != CTWS_OK) return r;
-    if ((r = grow(h, h->rg_tmp, std::max(tb_sort, tb_rle))) != CTWS_OK) return r;
-    o->sids = (uint64_t*)h->rg_skeys.p;
-    o->srecs = (uint64_t*)h->rg_sw.p;
-    o->uniq = (uint64_t*)h->rg_keys.p;
-    o->counts = (uint64_t*)h->rg_sum.p;
-    uint64_t* nruns = (uint64_t*)h->rg_red.p + kRedRuns;
-    HIPCHK(pair_sort(h->rg_tmp.p, tb_sort, ids, o->sids, recs, o->srecs, n, bits, h->stream));
-    HIPCHK(u64_runs(h->rg_tmp.p, tb_rle, o->sids, o->uniq, o->counts, nruns, n, h->stream));
-    record(h, ev);
-    unsigned long long runs = 0;
-    HIPCHK(hipMemcpyAsync(&runs, nruns, sizeof(runs), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (runs == 0 || runs > (unsigned long long)n) {
-        h->err = std::string(what) + ": " + std::to_string(runs) + " ids from " + std::to_string(n) + " runs";
-        return CTWS_EHIP;
-    }
-    o->m = (int64_t)runs;
-    return CTWS_OK;
-}
-
-// ---- GraphWorkflow: the region adjacency graph (k_rag.hip) ----------------------------------
-// The sorted distinct values of dv (device) into rg_tab, by the relabel path's radix sort and
-// run-length encoding: these are id tables with many repeats of few values over a narrow range,
-// where the bitmap unique's atomics all land in a few words (57 ms for the 16.8 M labels of a
-// block of fragments, measured).  The table grows to the size the first call reports.
-int rag_table(ctws_handle* h, const uint64_t* dv, int64_t n, int64_t* nt) {
-    int r;
-    *nt = 0;
-    if (n == 0) return CTWS_OK;
-    const int64_t cap = std::max<int64_t>((int64_t)(h->rg_tab.bytes / sizeof(uint64_t)), 1 << 16);
-    if ((r = grow(h, h->rg_tab, sizeof(uint64_t) * (size_t)cap)) != CTWS_OK) return r;
-    r = unique_sorted(h, dv, n, 1, (uint64_t*)h->rg_tab.p, nullptr, cap, nt);
-    if (r == CTWS_EINVAL && *nt > cap) {
-        const int64_t want = *nt;
-        h->err.clear();
-        if ((r = grow(h, h->rg_tab, sizeof(uint64_t) * (size_t)want)) != CTWS_OK) return r;
-        r = unique_sorted(h, dv, n, 1, (uint64_t*)h->rg_tab.p, nullptr, want, nt);
-    }
-    return r;
-}
-
-// The tail both entry points share: n (pair, weight) records on the device -> the sorted unique
-// pairs in rg_out (m x 2) with their summed weights in rg_sum (m).  tab (device, ascending)
-// holds every endpoint value; weights == nullptr counts 1 per record.
-int pairs_tail(ctws_handle* h, const uint64_t* pairs, const uint64_t* weights, int64_t n, const uint64_t* tab,
-               int64_t nt, int64_t* m) {
-    *m = 0;
-    if (n == 0) return CTWS_OK;
-    if (n >= (1ll << 31)) {
-        h->err = "unique pairs: more than 2^31 - 1 pairs in one call";
-        return CTWS_EUNSUPPORTED;
-    }
-    if (nt >= (1ll << 32)) {
-        h->err = "unique pairs: 2^32 or more distinct ids in one call (the sort keys hold two 32-bit ranks)";
-        return CTWS_EUNSUPPORTED;
-    }
-    int b = 1;  // bits per rank
-    while ((1ll << b) < nt) ++b;
-    int r;
-    const size_t nb = sizeof(uint64_t) * (size_t)n;
-    size_t tb_sort = 0, tb_red = 0;
-    HIPCHK(pair_sort(nullptr, tb_sort, nullptr, nullptr, nullptr, nullptr, n, 2 * b, h->stream));
-    HIPCHK(pair_reduce(nullptr, tb_red, nullptr, nullptr, nullptr, nullptr, nullptr, n, h->stream));
-    if ((r = grow(h, h->rg_keys, nb)) != CTWS_OK) return r;
-    if ((r = grow(h, h->rg_skeys, nb)) != CTWS_OK) return r;
-    if ((r = grow(h, h->rg_sw, nb)) != CTWS_OK) return r;
-    if ((r = grow(h, h->rg_sum, nb)) != CTWS_OK) return r;
-    if ((r = grow(h, h->rg_tmp, std::max(tb_sort, tb_red))) != CTWS_OK) return r;
-    if ((r = grow(h, h->rg_red, kRedWords * sizeof(uint64_t))) != CTWS_OK) return r;
-    if (!weights && (r = grow(h, h->rg_w, nb)) != CTWS_OK) return r;
-    uint64_t* keys = (uint64_t*)h->rg_keys.p;
-    uint64_t* skeys = (uint64_t*)h->rg_skeys.p;
-    uint64_t* sw = (uint64_t*)h->rg_sw.p;
-    uint64_t* sums = (uint64_t*)h->rg_sum.p;
-    unsigned long long* red = (unsigned long long*)h->rg_red.p;
-    const unsigned g = (unsigned)std::min<int64_t>((n + 255) / 256, 8192);
-    HIPCHK(hipMemsetAsync(red + kRedPairRuns, 0, 2 * sizeof(uint64_t), h->stream));  // (and kRedPairMiss)
-    record(h, 2);
-    if (!weights) {
-        k_pair_ones<<<g, 256, 0, h->stream>>>((uint64_t*)h->rg_w.p, n);
-        weights = (const uint64_t*)h->rg_w.p;
-    }
-    k_pair_keys<<<g, 256, 0, h->stream>>>(pairs, n, tab, nt, b, keys, red + kRedPairMiss);
-    LAUNCHCHK();
-    record(h, 3);
-    HIPCHK(pair_sort(h->rg_tmp.p, tb_sort, keys, skeys, weights, sw, n, 2 * b, h->stream));
-    record(h, 4);
-    // (the unsorted keys are dead: their buffer takes the unique keys)
-    HIPCHK(pair_reduce(h->rg_tmp.p, tb_red, skeys, keys, sw, sums, (uint64_t*)(red + kRedPairRuns), n,
-                       h->stream));
-    record(h, 5);
-    unsigned long long hr[2] = {0ull, 0ull};
-    HIPCHK(hipMemcpyAsync(hr, red + kRedPairRuns, sizeof(hr), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (hr[1]) {
-        h->err = "unique pairs: " + std::to_string(hr[1]) + " endpoint values are missing from the id table";
-        return CTWS_EINVAL;
-    }
-    *m = (int64_t)hr[0];
-    if ((r = grow(h, h->rg_out, 2 * sizeof(uint64_t) * (size_t)*m)) != CTWS_OK) return r;
-    const unsigned gm = (unsigned)std::min<int64_t>((*m + 255) / 256, 8192);
-    k_pair_unpack<<<gm, 256, 0, h->stream>>>(keys, *m, tab, b, (uint64_t*)h->rg_out.p);
-    LAUNCHCHK();
-    record(h, 6);
-    HIPCHK(hipStreamSynchronize(h->stream));
-    stage_time(h, "pair_keys", 2, 3);
-    stage_time(h, "pair_sort", 3, 4);
-    stage_time(h, "pair_reduce", 4, 5);
-    stage_time(h, "pair_unpack", 5, 6);
-    return CTWS_OK;
-}
-
-// the tail's result -> the caller's buffers (the sizes are known to fit)
-int pairs_out(ctws_handle* h, int64_t m, int on_device, uint64_t* out, uint64_t* counts) {
-    if (m) {
-        const hipMemcpyKind k = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-        HIPCHK(hipMemcpyAsync(out, h->rg_out.p, 2 * sizeof(uint64_t) * (size_t)m, k, h->stream));
-        if (counts) HIPCHK(hipMemcpyAsync(counts, h->rg_sum.p, sizeof(uint64_t) * (size_t)m, k, h->stream));
-    }
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return CTWS_OK;
-}
-
-int rag_block(ctws_handle* h, const uint64_t* labels, int64_t nz, int64_t ny, int64_t nx, int ignore_label,
-              uint64_t* nodes, int64_t cap_nodes, int64_t* n_nodes, uint64_t* edges, uint64_t* counts,
-              int64_t cap_edges, int64_t* n_edges, bool dev) {
-    if (!h || !labels || nz <= 0 || ny <= 0 || nx <= 0 || !n_nodes || !n_edges || cap_nodes < 0 || cap_edges < 0 ||
-        (!nodes && cap_nodes > 0) || (!edges && cap_edges > 0))
-        return CTWS_EINVAL;
-    int r;
-    if ((r = call_begin(h)) != CTWS_OK) return r;
-    *n_nodes = *n_edges = 0;
-    r = check_extent(h, nz, ny, nx, "rag block", "block", "the pair kernel indexes a block with 32 bits");
-    if (r != CTWS_OK) return r;
-    const int64_t N = nz * ny * nx;
-    const uint64_t* dl;
-    if ((r = stage_in(h, h->rg_lab, labels, sizeof(uint64_t) * (size_t)N, dev, &dl)) != CTWS_OK) return r;
-    // one pass emits the pairs and the node ids, into first buffers of a quarter / a sixteenth of
-    // the voxels
-    if ((r = grow(h, h->rg_red, kRedWords * sizeof(uint64_t))) != CTWS_OK) return r;
-    unsigned long long* cnt = (unsigned long long*)h->rg_red.p;
-    RagArgs a;
-    a.lab = dl;
-    a.nz = (uint32_t)nz;
-    a.ny = (uint32_t)ny;
-    a.nx = (uint32_t)nx;
-    a.ignore = ignore_label ? 1 : 0;
-    a.count = cnt;
-    a.ncount = cnt + kRedNodes;
-    const int64_t rows = nz * ny;
-    // four workgroups per CU (their LDS stages) and no more: every wave ends with an append of
-    // its own, and one counter word takes only ~85 returning atomics per microsecond
-    const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>((rows + 3) / 4, 1024));
-    EmitCap caps[2] = {{kRedEmit, first_cap(N, 4)}, {kRedNodes, first_cap(N, 16)}};
-    Emitted e;
-    record(h, 0);
-    r = counted_emit(
-        h, "rag block", cnt, kRedNodes + 1, kRedNodes + 1, caps, 2,
-        [&] {
-            int r;
-            if ((r = grow(h, h->rg_pairs, 2 * sizeof(uint64_t) * (size_t)caps[0].cap)) != CTWS_OK) return r;
-            if ((r = grow(h, h->rg_w, sizeof(uint64_t) * (size_t)caps[0].cap)) != CTWS_OK) return r;
-            if ((r = grow(h, h->rg_nodes, sizeof(uint64_t) * (size_t)caps[1].cap)) != CTWS_OK) return r;
-            a.pairs = (uint64_t*)h->rg_pairs.p;
-            a.weights = (uint64_t*)h->rg_w.p;
-            a.nodes = (uint64_t*)h->rg_nodes.p;
-            a.cap = caps[0].cap;
-            a.ncap = caps[1].cap;
-            k_rag_pairs<<<g, 256, 0, h->stream>>>(a);
-            return CTWS_OK;
-        },
-        [](const unsigned long long*) { return CTWS_OK; }, &e);
-    if (r != CTWS_OK) return r;
-    const int64_t n_pairs = (int64_t)e.w[kRedEmit], n_ids = (int64_t)e.w[kRedNodes];
-    record(h, 1);
-    // nodes: the sorted unique of the emitted ids = np.unique of the block (without 0 under
-    // ignore_label: the kernel emits no 0 then)
-    int64_t nt = 0;
-    if ((r = rag_table(h, (const uint64_t*)h->rg_nodes.p, n_ids, &nt)) != CTWS_OK) return r;
-    const uint64_t* tab = (const uint64_t*)h->rg_tab.p;
-    record(h, 7);
-    HIPCHK(hipStreamSynchronize(h->stream));
-    stage_time(h, "rag_pairs", 0, 1);
-    stage_time(h, "rag_nodes", 1, 7);
-    add_timing(h, "rag_pair_passes", (float)e.passes);  // (counts, as the flood's rounds)
-    add_timing(h, "rag_emits", (float)n_pairs);
-    add_timing(h, "rag_node_emits", (float)n_ids);
-    int64_t m = 0;
-    if ((r = pairs_tail(h, (const uint64_t*)h->rg_pairs.p, (const uint64_t*)h->rg_w.p, n_pairs, tab, nt, &m)) !=
-        CTWS_OK)
-        return r;
-    *n_nodes = nt;
-    *n_edges = m;
-    if (*n_nodes > cap_nodes || m > cap_edges) {
-        h->err = "rag block: output capacity too small";
-        return CTWS_EINVAL;
-    }
-    if (*n_nodes)
-        HIPCHK(hipMemcpyAsync(nodes, tab, sizeof(uint64_t) * (size_t)*n_nodes,
-                              dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
-    return pairs_out(h, m, dev ? 1 : 0, edges, counts);
-}
-}  // namespace
-}  // extern "C++"
-
-int ctws_unique_pairs_u64(ctws_handle* h, const uint64_t* pairs, const uint64_t* weights, int64_t n, int on_device,
-                          uint64_t* out, uint64_t* counts, int64_t cap, int64_t* n_unique) {
-    if (!h || (!pairs && n > 0) || n < 0 || !n_unique || cap < 0 || (!out && cap > 0)) return CTWS_EINVAL;
-    int r;
-    if ((r = call_begin(h)) != CTWS_OK) return r;
-    *n_unique = 0;
-    if (n == 0) return CTWS_OK;
-    if (n >= (1ll << 30)) {
-        h->err = "unique pairs: 2^30 or more pairs in one call";
-        return CTWS_EUNSUPPORTED;
-    }
-    const bool dev = on_device != 0;
-    if ((r = stage_in(h, h->rg_pairs, pairs, 2 * sizeof(uint64_t) * (size_t)n, dev, &pairs)) != CTWS_OK) return r;
-    if (weights && (r = stage_in(h, h->rg_lab, weights, sizeof(uint64_t) * (size_t)n, dev, &weights)) != CTWS_OK)
-        return r;
-    // ids -> ranks: the distinct endpoint values
-    int64_t nt = 0;
-    if ((r = rag_table(h, pairs, 2 * n, &nt)) != CTWS_OK) return r;
-    int64_t m = 0;
-    if ((r = pairs_tail(h, pairs, weights, n, (const uint64_t*)h->rg_tab.p, nt, &m)) != CTWS_OK) return r;
-    *n_unique = m;
-    if (m > cap) {
-        h->err = "ctws_unique_pairs_u64: output capacity too small";
-        return CTWS_EINVAL;
-    }
-    return pairs_out(h, m, on_device, out, counts);
-}
-
-int ctws_rag_block(ctws_handle* h, const uint64_t* labels, int64_t nz, int64_t ny, int64_t nx, int ignore_label,
-                   uint64_t* nodes, int64_t cap_nodes, int64_t* n_nodes, uint64_t* edges, uint64_t* counts,
-                   int64_t cap_edges, int64_t* n_edges) {
-    return rag_block(h, labels, nz, ny, nx, ignore_label, nodes, cap_nodes, n_nodes, edges, counts, cap_edges, n_edges,
-                     false);
-}
-
-int ctws_rag_block_device(ctws_handle* h, const uint64_t* labels, int64_t nz, int64_t ny, int64_t nx, int ignore_label,
-                          uint64_t* nodes, int64_t cap_nodes, int64_t* n_nodes, uint64_t* edges, uint64_t* counts,
-                          int64_t cap_edges, int64_t* n_edges) {
-    return rag_block(h, labels, nz, ny, nx, ignore_label, nodes, cap_nodes, n_nodes, edges, counts, cap_edges, n_edges,
-                     true);
-}
-
-
-// ---- NodeLabelWorkflow: fragment / label overlaps (k_overlaps.hip) ---------------------------
-extern "C++" {
-namespace {
-int label_overlaps(ctws_handle* h, const uint64_t* nodes_vol, const uint64_t* labels_vol, int64_t n, int with_ignore,
-                   uint64_t ignore_label, uint64_t* rows, int64_t cap, int64_t* n_rows, bool dev) {
-    if (!h || n < 0 || ((!nodes_vol || !labels_vol) && n > 0) || !n_rows || cap < 0 || (!rows && cap > 0))
-        return CTWS_EINVAL;
-    int r;
-    if ((r = call_begin(h)) != CTWS_OK) return r;
-    *n_rows = 0;
-    if (n == 0) return CTWS_OK;
-    r = check_extent(h, 1, 1, n, "label overlaps", "call", "the pair kernel indexes the arrays with 32 bits");
-    if (r != CTWS_OK) return r;
-    const size_t nb = sizeof(uint64_t) * (size_t)n;
-    const uint64_t *dn, *dl;
-    if ((r = stage_in(h, h->rg_lab, nodes_vol, nb, dev, &dn)) != CTWS_OK) return r;
-    if ((r = stage_in(h, h->ov_lab, labels_vol, nb, dev, &dl)) != CTWS_OK) return r;
-    // the run heads, at most one per voxel, into a first buffer of a quarter of the voxels
-    if ((r = grow(h, h->rg_red, kRedWords * sizeof(uint64_t))) != CTWS_OK) return r;
-    unsigned long long* cnt = (unsigned long long*)h->rg_red.p;
-    OvArgs a;
-    a.nodes = dn;
-    a.labels = dl;
-    a.n = (uint32_t)n;
-    a.with_ignore = with_ignore ? 1 : 0;
-    a.ignore_label = ignore_label;
-    a.count = cnt;
-    const int64_t words = (n + 63) / 64;
-    // four workgroups per CU, as k_rag_pairs: every wave ends with an append of its own
-    const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>((words + 3) / 4, 1024));
-    EmitCap ecap = {kRedEmit, first_cap(n, 4)};
-    Emitted e;
-    record(h, 0);
-    r = counted_emit(
-        h, "label overlaps", cnt, 1, 1, &ecap, 1,
-        [&] {
-            int r;
-            if ((r = grow(h, h->rg_pairs, 2 * sizeof(uint64_t) * (size_t)ecap.cap)) != CTWS_OK) return r;
-            if ((r = grow(h, h->rg_w, sizeof(uint64_t) * (size_t)ecap.cap)) != CTWS_OK) return r;
-            a.pairs = (uint64_t*)h->rg_pairs.p;
-            a.weights = (uint64_t*)h->rg_w.p;
-            a.cap = ecap.cap;
-            k_ov_pairs<<<g, 256, 0, h->stream>>>(a);
-            return CTWS_OK;
-        },
-        [&](const unsigned long long* w) { return runs_within(h, "label overlaps", w[kRedEmit], 0, n); }, &e);
-    if (r != CTWS_OK) return r;
-    const unsigned long long emitted = e.w[kRedEmit];
-    record(h, 1);
-    HIPCHK(hipStreamSynchronize(h->stream));
-    stage_time(h, "ov_pairs", 0, 1);
-    add_timing(h, "ov_pair_passes", (float)e.passes);  // (counts, as the flood's rounds)
-    add_timing(h, "ov_emits", (float)emitted);
-    if (emitted == 0) return CTWS_OK;  // every voxel carries the ignore label
-    if (emitted >= (1ull << 30)) {
-        h->err = "label overlaps: 2^30 or more runs of equal (node, label) pairs in one call";
-        return CTWS_EUNSUPPORTED;
-    }
-    // ids -> ranks in one table for both sides: the key order is the (node, label) order
-    int64_t nt = 0, m = 0;
-    if ((r = rag_table(h, (const uint64_t*)h->rg_pairs.p, 2 * (int64_t)emitted, &nt)) != CTWS_OK) return r;
-    record(h, 7);
-    HIPCHK(hipStreamSynchronize(h->stream));
-    stage_time(h, "ov_table", 1, 7);
-    if ((r = pairs_tail(h, (const uint64_t*)h->rg_pairs.p, (const uint64_t*)h->rg_w.p, (int64_t)emitted,
-                        (const uint64_t*)h->rg_tab.p, nt, &m)) != CTWS_OK)
-        return r;
-    *n_rows = m;
-    if (m > cap) {
-        h->err = "label overlaps: output capacity too small";
-        return CTWS_EINVAL;
-    }
-    const size_t rb = 3 * sizeof(uint64_t) * (size_t)m;
-    uint64_t* drows;
-    if ((r = out_begin(h, h->ov_rows, rows, rb, dev, &drows)) != CTWS_OK) return r;
-    const unsigned gm = (unsigned)std::min<int64_t>((m + 255) / 256, 8192);
-    k_ov_rows<<<gm, 256, 0, h->stream>>>((const uint64_t*)h->rg_out.p, (const uint64_t*)h->rg_sum.p, m, drows);
-    LAUNCHCHK();
-    return out_end(h, rows, drows, rb, dev);
-}
-}  // namespace
-}  // extern "C++"
-
-int ctws_label_overlaps(ctws_handle* h, const uint64_t* nodes_vol, const uint64_t* labels_vol, int64_t n,
-                        int with_ignore, uint64_t ignore_label, uint64_t* rows, int64_t cap, int64_t* n_rows) {
-    return label_overlaps(h, nodes_vol, labels_vol, n, with_ignore, ignore_label, rows, cap, n_rows, false);
-}
-
-int ctws_label_overlaps_device(ctws_handle* h, const uint64_t* nodes_vol, const uint64_t* labels_vol, int64_t n,
-                               int with_ignore, uint64_t ignore_label, uint64_t* rows, int64_t cap, int64_t* n_rows) {
-    return label_overlaps(h, nodes_vol, labels_vol, n, with_ignore, ignore_label, rows, cap, n_rows, true);
-}
-
-// ---- MorphologyWorkflow: size, centre and bounding box per id (k_morph.hip) ------------------
-extern "C++" {
-namespace {
-int block_morphology(ctws_handle* h, const uint64_t* labels, int64_t nz, int64_t ny, int64_t nx, const int64_t* begin,
-                     double* rows, int64_t cap, int64_t* n_rows, bool dev) {
-    if (!h || !labels || nz <= 0 || ny <= 0 || nx <= 0 || !begin || !n_rows || cap < 0 || (!rows && cap > 0))
-        return CTWS_EINVAL;
-    int r;
-    if ((r = call_begin(h)) != CTWS_OK) return r;
-    *n_rows = 0;
-    if (begin[0] < 0 || begin[1] < 0 || begin[2] < 0) {
-        h->err = "block morphology: a negative begin";
-        return CTWS_EINVAL;
-    }
-    // the record packs z, y, x0 into 19 bits each; begin + extent <= 2^21 and fewer than 2^31
-    // voxels keep every coordinate sum below 2^52, exact in a double
-    constexpr int64_t kExt = 1ll << 19, kCoord = 1ll << 21;
-    if (nz >= kExt || ny >= kExt || nx >= kExt) {
-        h->err = "block morphology: an extent of 2^19 or more (the run record holds 19 bits per coordinate)";
-        return CTWS_EUNSUPPORTED;
-    }
-    r = check_extent(h, nz, ny, nx, "block morphology", "block", "the run kernel indexes a block with 32 bits");
-    if (r != CTWS_OK) return r;
-    const int64_t ext[3] = {nz, ny, nx};
-    for (int d = 0; d < 3; ++d)
-        if (begin[d] > kCoord || begin[d] + ext[d] > kCoord) {
-            h->err = "block morphology: begin + extent above 2^21 (the coordinate sums would not be exact doubles)";
-            return CTWS_EUNSUPPORTED;
-        }
-    const int64_t N = nz * ny * nx;
-    const uint64_t* dl;
-    if ((r = stage_in(h, h->rg_lab, labels, sizeof(uint64_t) * (size_t)N, dev, &dl)) != CTWS_OK) return r;
-    // the run heads, at least one and at most one per voxel, into a first buffer of a quarter of
-    // the voxels
-    if ((r = grow(h, h->rg_red, kRedWords * sizeof(uint64_t))) != CTWS_OK) return r;
-    unsigned long long* cnt = (unsigned long long*)h->rg_red.p;
-    MorphArgs a;
-    a.lab = dl;
-    a.nz = (uint32_t)nz;
-    a.ny = (uint32_t)ny;
-    a.nx = (uint32_t)nx;
-    a.count = cnt;
-    a.vmax = cnt + kRedVmax;
-    const int64_t lines = nz * ny;
-    // four workgroups per CU, as k_rag_pairs: every wave ends with an append of its own
-    const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>((lines + 3) / 4, 1024));
-    EmitCap ecap = {kRedEmit, first_cap(N, 4)};
-    Emitted e;
-    record(h, 0);
-    r = counted_emit(
-        h, "block morphology", cnt, kRedVmax + 1, kRedVmax + 1, &ecap, 1,
-        [&] {
-            int r;
-            if ((r = grow(h, h->rg_pairs, sizeof(uint64_t) * (size_t)ecap.cap)) != CTWS_OK) return r;
-            if ((r = grow(h, h->rg_w, sizeof(uint64_t) * (size_t)ecap.cap)) != CTWS_OK) return r;
-            a.ids = (uint64_t*)h->rg_pairs.p;
-            a.recs = (uint64_t*)h->rg_w.p;
-            a.cap = ecap.cap;
-            k_morph_runs<<<g, 256, 0, h->stream>>>(a);
-            return CTWS_OK;
-        },
-        [&](const unsigned long long* w) { return runs_within(h, "block morphology", w[kRedEmit], 1, N); }, &e);
-    if (r != CTWS_OK) return r;
-    const int64_t n = (int64_t)e.w[kRedEmit];  // (< 2^31)
-    record(h, 1);
-    // the largest id was taken by the run pass
-    ById s;
-    if ((r = sort_by_id(h, "block morphology", a.ids, a.recs, n, e.w[kRedVmax], 2, &s)) != CTWS_OK) return r;
-    stage_time(h, "morph_runs", 0, 1);
-    stage_time(h, "morph_sort", 1, 2);
-    add_timing(h, "morph_run_passes", (float)e.passes);  // (counts, as the flood's rounds)
-    add_timing(h, "morph_emits", (float)n);
-    const int64_t m = s.m;
-    *n_rows = m;
-    if (m > cap) {
-        h->err = "block morphology: output capacity too small";
-        return CTWS_EINVAL;
-    }
-    const size_t rb = 11 * sizeof(double) * (size_t)m;
-    double* drows;
-    if ((r = out_begin(h, h->mo_rows, rows, rb, dev, &drows)) != CTWS_OK) return r;
-    // the per-id table of the split segments: ten integers per id, zero = neutral
-    const size_t ab = 10 * sizeof(uint64_t) * (size_t)m;
-    if ((r = grow(h, h->mo_acc, ab)) != CTWS_OK) return r;
-    unsigned long long* acc = (unsigned long long*)h->mo_acc.p;
-    HIPCHK(hipMemsetAsync(acc, 0, ab, h->stream));
-    const MorphBegin b = {(uint64_t)begin[0], (uint64_t)begin[1], (uint64_t)begin[2]};
-    const int64_t waves = m + n / kMorphChunk;  // a wave per id and per whole chunk of records
-    const unsigned gm = (unsigned)std::max<int64_t>(1, std::min<int64_t>((waves + 3) / 4, 2048));
-    k_morph_rows<<<gm, 256, 0, h->stream>>>(s.sids, s.srecs, (uint32_t)n, s.uniq, s.counts, (uint32_t)m, b, acc, drows);
-    LAUNCHCHK();
-    if (n >= (int64_t)kMorphChunk) {  // (a shorter record list holds no whole chunk: no split segment)
-        const unsigned gl = (unsigned)std::min<int64_t>((m + 255) / 256, 1024);
-        k_morph_long_rows<<<gl, 256, 0, h->stream>>>(s.uniq, (uint32_t)m, b, acc, drows);
-        LAUNCHCHK();
-    }
-    record(h, 3);
-    if ((r = out_end(h, rows, drows, rb, dev)) != CTWS_OK) return r;
-    stage_time(h, "morph_rows", 2, 3);
-    return CTWS_OK;
-}
-}  // namespace
-}  // extern "C++"
-
-int ctws_block_morphology(ctws_handle* h, const uint64_t* labels, int64_t nz, int64_t ny, int64_t nx,
-                          const int64_t begin[3], double* rows, int64_t cap, int64_t* n_rows) {
-    return block_morphology(h, labels, nz, ny, nx, begin, rows, cap, n_rows, false);
-}
-
-int ctws_block_morphology_device(ctws_handle* h, const uint64_t* labels, int64_t nz, int64_t ny, int64_t nx,
-                                 const int64_t begin[3], double* rows, int64_t cap, int64_t* n_rows) {
-    return block_morphology(h, labels, nz, ny, nx, begin, rows, cap, n_rows, true);
-}
-
-// ---- RegionFeaturesWorkflow: count and mean input value per id (k_regfeat.hip) --------------
-extern "C++" {
-namespace {
-int region_features_block(ctws_handle* h, const uint64_t* labels, const void* data, int data_dtype, int64_t nz,
-                          int64_t ny, int64_t nx, int with_ignore, uint64_t ignore_label, double* rows, int64_t cap,
-                          int64_t* n_rows, bool dev) {
-    if (!h || !labels || !data || nz <= 0 || ny <= 0 || nx <= 0 || !n_rows || cap < 0 || (!rows && cap > 0))
-        return CTWS_EINVAL;
-    int r;
-    if ((r = call_begin(h)) != CTWS_OK) return r;
-    *n_rows = 0;
-    if (data_dtype != CTWS_U8 && data_dtype != CTWS_U16 && data_dtype != CTWS_F32 && data_dtype != CTWS_F64) {
-        h->err = "region features: the input map is uint8, uint16, float32 or float64";
-        return CTWS_EINVAL;
-    }
-    r = check_extent(h, nz, ny, nx, "region features", "block", "the kernels index a block with 32 bits");
-    if (r != CTWS_OK) return r;
-    const int64_t N = nz * ny * nx, lines = nz * ny;
-    if (lines + 1 >= (1ll << 31)) {  // (the scan takes the rows' counts and one 0 behind them with a 32-bit size)
-        h->err = "region features: 2^31 - 1 rows in one block (the scan of the rows' run counts is 32-bit)";
-        return CTWS_EUNSUPPORTED;
-    }
-    const size_t es = data_dtype == CTWS_U8 ? 1 : data_dtype == CTWS_U16 ? 2 : data_dtype == CTWS_F32 ? 4 : 8;
-    const uint64_t* dl;
-    const void* dd;
-    if ((r = stage_in(h, h->rg_lab, labels, sizeof(uint64_t) * (size_t)N, dev, &dl)) != CTWS_OK) return r;
-    if ((r = stage_in(h, h->rf_data, data, es * (size_t)N, dev, &dd)) != CTWS_OK) return r;
-    if ((r = grow(h, h->rg_red, kRedWords * sizeof(uint64_t))) != CTWS_OK) return r;
-    unsigned long long* red = (unsigned long long*)h->rg_red.p;
-    // the rows' run counts with one 0 behind them: the scan's last entry is the total
-    const size_t cb = sizeof(uint32_t) * (size_t)(lines + 1);
-    size_t tb_scan = 0;
-    HIPCHK(u32_exclusive_sum(nullptr, tb_scan, nullptr, nullptr, lines + 1, h->stream));
-    if ((r = grow(h, h->rf_cnt, cb)) != CTWS_OK) return r;
-    if ((r = grow(h, h->rf_off, cb)) != CTWS_OK) return r;
-    if ((r = grow(h, h->rg_tmp, tb_scan)) != CTWS_OK) return r;
-    uint32_t* rcnt = (uint32_t*)h->rf_cnt.p;
-    uint32_t* roff = (uint32_t*)h->rf_off.p;
-    // four workgroups per CU, a wave per row
-    const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>((lines + 3) / 4, 1024));
-    record(h, 0);
-    HIPCHK(hipMemsetAsync(rcnt + lines, 0, sizeof(uint32_t), h->stream));
-    HIPCHK(hipMemsetAsync(red, 0, kRedWords * sizeof(uint64_t), h->stream));
-    k_regfeat_count<<<g, 256, 0, h->stream>>>(dl, (uint32_t)lines, (uint32_t)nx, rcnt);
-    LAUNCHCHK();
-    HIPCHK(u32_exclusive_sum(h->rg_tmp.p, tb_scan, rcnt, roff, lines + 1, h->stream));
-    record(h, 1);
-    uint32_t total = 0;
-    HIPCHK(hipMemcpyAsync(&total, roff + lines, sizeof(total), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (total == 0 || (int64_t)total > N) {
-        h->err = "region features: the count kernel found " + std::to_string(total) + " runs";
-        return CTWS_EHIP;
-    }
-    const int64_t n = (int64_t)total;  // (< 2^31): the record arrays hold exactly the runs
-    const size_t nb = sizeof(uint64_t) * (size_t)n;
-    if ((r = grow(h, h->rg_pairs, nb)) != CTWS_OK) return r;
-    if ((r = grow(h, h->rg_w, nb)) != CTWS_OK) return r;
-    if ((r = grow(h, h->rf_sums, sizeof(double) * (size_t)n)) != CTWS_OK) return r;
-    RegfeatArgs a;
-    a.lab = dl;
-    a.data = dd;
-    a.rows = (uint32_t)lines;
-    a.nx = (uint32_t)nx;
-    a.with_ignore = with_ignore ? 1 : 0;
-    a.ignore = ignore_label;
-    a.row_first = roff;
-    a.n = total;
-    a.ids = (uint64_t*)h->rg_pairs.p;
-    a.vals = (uint64_t*)h->rg_w.p;
-    a.sums = (double*)h->rf_sums.p;
-    a.vmax = red + kRedVmax;
-    if (data_dtype == CTWS_U8) k_regfeat_runs<uint8_t><<<g, 256, 0, h->stream>>>(a);
-    else if (data_dtype == CTWS_U16) k_regfeat_runs<uint16_t><<<g, 256, 0, h->stream>>>(a);
-    else if (data_dtype == CTWS_F32) k_regfeat_runs<float><<<g, 256, 0, h->stream>>>(a);
-    else k_regfeat_runs<double><<<g, 256, 0, h->stream>>>(a);
-    LAUNCHCHK();
-    record(h, 2);
-    unsigned long long vmax = 0;  // the largest id
-    HIPCHK(hipMemcpyAsync(&vmax, red + kRedVmax, sizeof(vmax), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    ById s;
-    if ((r = sort_by_id(h, "region features", a.ids, a.vals, n, vmax, 3, &s)) != CTWS_OK) return r;
-    stage_time(h, "regfeat_count", 0, 1);
-    stage_time(h, "regfeat_runs", 1, 2);
-    stage_time(h, "regfeat_sort", 2, 3);
-    add_timing(h, "regfeat_records", (float)total);  // (a count, as the flood's rounds)
-    const int64_t m = s.m;
-    *n_rows = m;
-    if (m > cap) {
-        h->err = "region features: output capacity too small";
-        return CTWS_EINVAL;
-    }
-    const size_t rb = 3 * sizeof(double) * (size_t)m;
-    double* drows;
-    if ((r = out_begin(h, h->rf_rows, rows, rb, dev, &drows)) != CTWS_OK) return r;
-    // the chunk table: (n, sum) per whole aligned chunk of sorted records, the n first
-    const int64_t chunks = n / kRegfeatChunk;
-    if ((r = grow(h, h->rf_ctab, 2 * sizeof(uint64_t) * (size_t)std::max<int64_t>(1, chunks))) != CTWS_OK) return r;
-    uint64_t* chunk_n = (uint64_t*)h->rf_ctab.p;
-    double* chunk_s = (double*)(chunk_n + std::max<int64_t>(1, chunks));
-    if (chunks > 0) {
-        const unsigned gc = (unsigned)std::min<int64_t>((chunks + 3) / 4, 2048);
-        k_regfeat_chunks<<<gc, 256, 0, h->stream>>>(s.sids, s.srecs, a.sums, total, chunk_n, chunk_s);
-        LAUNCHCHK();
-    }
-    const unsigned gm = (unsigned)std::max<int64_t>(1, std::min<int64_t>((m + 3) / 4, 2048));
-    k_regfeat_rows<<<gm, 256, 0, h->stream>>>(s.sids, s.srecs, a.sums, total, s.uniq, s.counts, (uint32_t)m, chunk_n,
-                                              chunk_s, drows);
-    LAUNCHCHK();
-    record(h, 4);
-    if ((r = out_end(h, rows, drows, rb, dev)) != CTWS_OK) return r;
-    stage_time(h, "regfeat_rows", 3, 4);
-    return CTWS_OK;
-}
-}  // namespace
-}  // extern "C++"
-
-int ctws_region_features_block(ctws_handle* h, const uint64_t* labels, const void* data, int data_dtype, int64_t nz,
-                               int64_t ny, int64_t nx, int with_ignore, uint64_t ignore_label, double* rows,
-                               int64_t cap, int64_t* n_rows) {
-    return region_features_block(h, labels, data, data_dtype, nz, ny, nx, with_ignore, ignore_label, rows, cap,
-                                 n_rows, false);
-}
-
-int ctws_region_features_block_device(ctws_handle* h, const uint64_t* labels, const void* data, int data_dtype,
-                                      int64_t nz, int64_t ny, int64_t nx, int with_ignore, uint64_t ignore_label,
-                                      double* rows, int64_t cap, int64_t* n_rows) {
-    return region_features_block(h, labels, data, data_dtype, nz, ny, nx, with_ignore, ignore_label, rows, cap,
-                                 n_rows, true);
-}
-
-// ---- DownscalingWorkflow: block reduction of one block (k_downscale.hip) ---------------------
-extern "C++" {
-namespace {
-using DsKernel = void (*)(DownscaleArgs);
-template <class T>
-DsKernel ds_kernel(int func, int variant) {  // variant 0: any factor, 1: (1, 2, 2), 2: (2, 2, 2)
-    static const DsKernel table[3][3] = {
-        {&k_downscale_cell<T, kDsMean>, &k_downscale_vec<T, kDsMean, 1>, &k_downscale_vec<T, kDsMean, 2>},
-        {&k_downscale_cell<T, kDsMax>, &k_downscale_vec<T, kDsMax, 1>, &k_downscale_vec<T, kDsMax, 2>},
-        {&k_downscale_cell<T, kDsMin>, &k_downscale_vec<T, kDsMin, 1>, &k_downscale_vec<T, kDsMin, 2>}};
-    return table[func][variant];
-}
-
-int downscale_block(ctws_handle* h, const void* input, int dtype, int64_t nz, int64_t ny, int64_t nx,
-                    const int64_t factors[3], int func, void* out, int64_t oz, int64_t oy, int64_t ox,
-                    int* any_nonzero, bool dev) {
-    int r;
-    if (!h) return CTWS_EINVAL;
-    if ((r = call_begin(h)) != CTWS_OK) return r;
-    if (!input || !out || !factors || !any_nonzero || nz <= 0 || ny <= 0 || nx <= 0) {
-        h->err = "downscale: bad arguments (a non-empty 3-D block, factors, an output and a flag)";
-        return CTWS_EINVAL;
-    }
-    *any_nonzero = 0;
-    if (dtype != CTWS_U8 && dtype != CTWS_U16 && dtype != CTWS_F32 && dtype != CTWS_F64) {
-        h->err = "downscale: the block is uint8, uint16, float32 or float64";
-        return CTWS_EINVAL;
-    }
-    if (func != kDsMean && func != kDsMax && func != kDsMin) {
-        h->err = "downscale: func is 0 (mean), 1 (max) or 2 (min)";
-        return CTWS_EINVAL;
-    }
-    for (int d = 0; d < 3; ++d)
-        if (factors[d] < 1 || factors[d] > 8) {
-            h->err = "downscale: every factor lies in 1..8";
-            return CTWS_EINVAL;
-        }
-    r = check_extent(h, nz, ny, nx, "downscale", "block", "the kernels index a block with 32 bits");
-    if (r != CTWS_OK) return r;
-    const int64_t fz = factors[0], fy = factors[1], fx = factors[2], n = fz * fy * fx;
-    if (oz != (nz + fz - 1) / fz || oy != (ny + fy - 1) / fy || ox != (nx + fx - 1) / fx) {
-        h->err = "downscale: the output extents are ceil(n / f) per axis";
-        return CTWS_EINVAL;
-    }
-    if (func == kDsMean && dtype == CTWS_U16 && n * 65535 >= (1ll << 24)) {
-        h->err = "downscale: the mean of " + std::to_string(n) + " uint16 voxels: the cell's sum can reach 2^24, where "
-                 "float32 no longer holds it exactly and the reference's summation order would decide the result";
-        return CTWS_EUNSUPPORTED;
-    }
-    const size_t es = dtype == CTWS_U8 ? 1 : dtype == CTWS_U16 ? 2 : dtype == CTWS_F32 ? 4 : 8;
-    const int64_t N = nz * ny * nx, M = oz * oy * ox;
-    const void* din;
-    void* dout;
-    if ((r = stage_in(h, h->ds_in, input, es * (size_t)N, dev, &din)) != CTWS_OK) return r;
-    if ((r = out_begin(h, h->ds_out, out, es * (size_t)M, dev, &dout)) != CTWS_OK) return r;
-    constexpr size_t kFlagBytes = sizeof(uint32_t) * kDsFlagSlots * kDsFlagStride;
-    if ((r = grow(h, h->ds_flag, kFlagBytes)) != CTWS_OK) return r;
-    DownscaleArgs a;
-    a.in = din;
-    a.out = dout;
-    a.nz = (uint32_t)nz, a.ny = (uint32_t)ny, a.nx = (uint32_t)nx;
-    a.oz = (uint32_t)oz, a.oy = (uint32_t)oy, a.ox = (uint32_t)ox;
-    a.fz = (uint32_t)fz, a.fy = (uint32_t)fy, a.fx = (uint32_t)fx;
-    a.flag = (uint32_t*)h->ds_flag.p;
-    const int variant = (fy == 2 && fx == 2 && fz <= 2) ? (int)fz : 0;
-    if (variant) {
-        const int64_t C = 16 / (int64_t)es;  // output voxels per lane
-        a.groups = (uint32_t)(nx / (2 * C));
-        a.per = a.groups + ((int64_t)a.groups * C < ox ? 1u : 0u);
-        a.items = (uint32_t)(oz * oy * (int64_t)a.per);  // (<= N)
-    } else {
-        a.groups = 0;
-        a.per = (uint32_t)ox;
-        a.items = (uint32_t)M;
-    }
-    const DsKernel k = dtype == CTWS_U8 ? ds_kernel<uint8_t>(func, variant)
-                       : dtype == CTWS_U16 ? ds_kernel<uint16_t>(func, variant)
-                       : dtype == CTWS_F32 ? ds_kernel<float>(func, variant)
-                                           : ds_kernel<double>(func, variant);
-    record(h, 0);
-    HIPCHK(hipMemsetAsync(a.flag, 0, kFlagBytes, h->stream));
-    k<<<(a.items + 255u) / 256u, 256, 0, h->stream>>>(a);
-    LAUNCHCHK();
-    record(h, 1);
-    h->ds_flags.resize((size_t)kDsFlagSlots * kDsFlagStride);
-    HIPCHK(hipMemcpyAsync(h->ds_flags.data(), a.flag, kFlagBytes, hipMemcpyDeviceToHost, h->stream));
-    if ((r = out_end(h, out, dout, es * (size_t)M, dev)) != CTWS_OK) return r;
-    uint32_t flag = 0;
-    for (int k = 0; k < kDsFlagSlots; ++k) flag |= h->ds_flags[(size_t)k * kDsFlagStride];
-    *any_nonzero = flag ? 1 : 0;
-    stage_time(h, "downscale", 0, 1);
-    return CTWS_OK;
-}
-}  // namespace
-}  // extern "C++"
-
-int ctws_downscale_block(ctws_handle* h, const void* input, int dtype, int64_t nz, int64_t ny, int64_t nx,
-                         const int64_t factors[3], int func, void* out, int64_t oz, int64_t oy, int64_t ox,
-                         int* any_nonzero) {
-    return downscale_block(h, input, dtype, nz, ny, nx, factors, func, out, oz, oy, ox, any_nonzero, false);
-}
-
-int ctws_downscale_block_device(ctws_handle* h, const void* input, int dtype, int64_t nz, int64_t ny, int64_t nx,
-                                const int64_t factors[3], int func, void* out, int64_t oz, int64_t oy, int64_t ox,
-                                int* any_nonzero) {
-    return downscale_block(h, input, dtype, nz, ny, nx, factors, func, out, oz, oy, ox, any_nonzero, true);
-}
-
-// ---- ImageFilter: Gaussian derivative filters of one block (k_imgfilter.hip) -----------------
-extern "C++" {
-namespace {
-// vigra Kernel1D<double>::initGaussianDerivative(sigma, order) restated (order 0: gaussian_taps):
-// the sampled derivative, its mean removed (vigra's DC removal), scaled so that the kernel's order-th
-// moment sum_x k(x) (-x)^n / n! is 1 (normalize(1.0, order)); a constant prefactor cancels there
-std::vector<double> filter_taps(double sigma, int order) {
-    if (order == 0) return gaussian_taps(sigma);
-    int radius = (int)((3.0 + 0.5 * order) * sigma + 0.5);
-    if (radius == 0) radius = 1;
-    const double s2 = sigma * sigma;
-    std::vector<double> k;
-    double sum = 0.0;
-    for (int x = -radius; x <= radius; ++x) {
-        const double xx = (double)x * (double)x;
-        const double e = std::exp(-xx / (2.0 * s2));
-        k.push_back(order == 1 ? -(double)x * e : (xx / s2 - 1.0) * e);
-        sum += k.back();
-    }
-    const double mean = sum / (double)k.size();
-    double moment = 0.0;
-    for (int x = -radius, i = 0; x <= radius; ++x, ++i) {
-        k[(size_t)i] -= mean;
-        moment += order == 1 ? k[(size_t)i] * -(double)x : k[(size_t)i] * ((double)x * (double)x) / 2.0;
-    }
-    for (double& v : k) v = v / moment;
-    return k;
-}
-bool if_sigma_ok(double s) { return s > 0.0 && s * 4.0 + 0.5 < 1073741824.0; }  // (also false for NaN)
-
-using IfKernel = void (*)(IfArgs);
-template <int NOUT>
-IfKernel if_first_pass(int dtype) {
-    return dtype == CTWS_U8    ? &k_if_col<uint8_t, 1, NOUT>
-           : dtype == CTWS_U16 ? &k_if_col<uint16_t, 1, NOUT>
-           : dtype == CTWS_F32 ? &k_if_col<float, 1, NOUT>
-                               : &k_if_col<double, 1, NOUT>;
-}
-
-int image_filter(ctws_handle* h, const void* data, int dtype, int64_t nz, int64_t ny, int64_t nx, int filter_id,
-                 const double* sigma, int apply_in_2d, int normalize, float* out, bool dev) {
-    int r;
-    if (!h) return CTWS_EINVAL;
-    if ((r = call_begin(h)) != CTWS_OK) return r;
-    if (!data || !out || !sigma || nz <= 0 || ny <= 0 || nx <= 0) {
-        h->err = "image filter: bad arguments (a non-empty 3-D block, three sigmas and an output)";
-        return CTWS_EINVAL;
-    }
-    if (dtype != CTWS_U8 && dtype != CTWS_U16 && dtype != CTWS_F32 && dtype != CTWS_F64) {
-        h->err = "image filter: the block is uint8, uint16, float32 or float64";
-        return CTWS_EINVAL;
-    }
-    if (filter_id != kIfSmooth && filter_id != kIfGradMag && filter_id != kIfLaplace) {
-        h->err = "image filter: filter_id is 0 (gaussianSmoothing), 1 (gaussianGradientMagnitude) or 2 "
-                 "(laplacianOfGaussian)";
-        return CTWS_EINVAL;
-    }
-    const int a0 = apply_in_2d ? 1 : 0;  // the first filtered axis
-    for (int a = a0; a < 3; ++a)
-        if (!if_sigma_ok(sigma[a])) {
-            h->err = "image filter: every sigma is positive (and below 2^28)";
-            return CTWS_EINVAL;
-        }
-    r = check_extent(h, nz, ny, nx, "image filter", "block", "the kernels index a block with 32 bits");
-    if (r != CTWS_OK) return r;
-    // the taps: per axis the smoothing taps and, for the derivative filters, those of the order
-    constexpr int kSlot = 2 * kIfMaxR + 1;
-    const int order = filter_id;  // 0, 1, 2
-    std::vector<double> htaps((size_t)6 * kSlot, 0.0);
-    int rad[3][2] = {{0, 0}, {0, 0}, {0, 0}}, rmax[3] = {0, 0, 0};
-    const int64_t ext[3] = {nz, ny, nx};
-    for (int a = a0; a < 3; ++a)
-        for (int w = 0; w < (order ? 2 : 1); ++w) {
-            const std::vector<double> k = filter_taps(sigma[a], w ? order : 0);
-            const int rr = (int)(k.size() / 2);
-            rad[a][w] = rr;
-            rmax[a] = std::max(rmax[a], rr);
-            if (ext[a] < (int64_t)rr + 1) {  // vigra: "kernel longer than line"
-                h->err = std::string("image filter: axis ") + "zyx"[a] + " holds " + std::to_string(ext[a]) +
-                         " voxels, fewer than the radius " + std::to_string(rr) + " + 1 of the order-" +
-                         std::to_string(w ? order : 0) + " taps (sigma " + std::to_string(sigma[a]) + ")";
-                return CTWS_EINVAL;
-            }
-            if (rr > kIfMaxR) {
-                h->err = "image filter: a tap radius of " + std::to_string(rr) + " along axis " + "zyx"[a] +
-                         ", above the " + std::to_string(kIfMaxR) + " the tiles hold";
-                return CTWS_EUNSUPPORTED;
-            }
-            std::copy(k.begin(), k.end(), htaps.begin() + (size_t)(2 * a + w) * kSlot);
-        }
-    auto slot = [&](int a, int w) { return (2 * a + w) * kSlot; };
-    const size_t es = dtype == CTWS_U8 ? 1 : dtype == CTWS_U16 ? 2 : dtype == CTWS_F32 ? 4 : 8;
-    const int64_t N = nz * ny * nx;
-    const void* din;
-    float* dout;
-    if ((r = stage_in(h, h->if_in, data, es * (size_t)N, dev, &din)) != CTWS_OK) return r;
-    if ((r = out_begin(h, h->if_out, out, sizeof(float) * (size_t)N, dev, &dout)) != CTWS_OK) return r;
-    const size_t fb = sizeof(float) * (size_t)N;
-    if ((r = grow(h, h->if_a, (order ? 2 : 1) * fb)) != CTWS_OK) return r;
-    if ((r = grow(h, h->if_b, (order ? 3 : 1) * fb)) != CTWS_OK) return r;
-    if ((r = grow(h, h->if_taps, sizeof(double) * htaps.size())) != CTWS_OK) return r;
-    if ((r = grow(h, h->if_mm, 2 * sizeof(uint32_t))) != CTWS_OK) return r;
-    if (h->if_taps_host != htaps) {
-        // (a blocking upload: the previous call has ended, nothing reads the taps now)
-        h->if_taps_host.clear();
-        HIPCHK(hipMemcpy(h->if_taps.p, htaps.data(), sizeof(double) * htaps.size(), hipMemcpyHostToDevice));
-        h->if_taps_host = htaps;
-    }
-    uint32_t* mm = (uint32_t*)h->if_mm.p;
-    float* A = (float*)h->if_a.p;
-    float* B = (float*)h->if_b.p;
-    record(h, 0);
-    if (normalize) {
-        HIPCHK(hipMemsetAsync(mm, 0xFF, sizeof(uint32_t), h->stream));
-        HIPCHK(hipMemsetAsync(mm + 1, 0, sizeof(uint32_t), h->stream));
-        const unsigned g = (unsigned)std::min<int64_t>((N + 255) / 256, 512);
-        if (dtype == CTWS_U8) k_if_minmax<uint8_t><<<g, 256, 0, h->stream>>>((const uint8_t*)din, N, mm);
-        else if (dtype == CTWS_U16) k_if_minmax<uint16_t><<<g, 256, 0, h->stream>>>((const uint16_t*)din, N, mm);
-        else if (dtype == CTWS_F32) k_if_minmax<float><<<g, 256, 0, h->stream>>>((const float*)din, N, mm);
-        else k_if_minmax<double><<<g, 256, 0, h->stream>>>((const double*)din, N, mm);
-        LAUNCHCHK();
-    }
-    record(h, 1);
-    IfArgs base{};
-    base.taps = (const double*)h->if_taps.p;
-    base.mm = mm;
-    base.nz = (int)nz, base.ny = (int)ny, base.nx = (int)nx;
-    auto col = [&](IfKernel k, IfArgs& a, int nin, int axis) {
-        a.axis = axis;
-        a.rmax = rmax[axis];
-        const int64_t L = ext[axis], other = axis == 0 ? ny : nz;
-        const int64_t tiles = other * ((L + kIfColTL - 1) / kIfColTL) * ((nx + kIfColW - 1) / kIfColW);
-        const size_t lds = sizeof(float) * (size_t)nin * (kIfColTL + 2 * a.rmax) * kIfColW;
-        k<<<(unsigned)tiles, 256, lds, h->stream>>>(a);
-    };
-    // the first pass reads the block in its own type, normalized on the fly
-    IfArgs p1 = base;
-    p1.in[0] = din;
-    p1.normalize = normalize ? 1 : 0;
-    const int af = a0;  // its axis
-    float* first_out = apply_in_2d ? B : A;
-    if (order) {  // D, S of the first axis
-        p1.out[0] = first_out, p1.out[1] = first_out + N;
-        p1.tap[0] = slot(af, 1), p1.rad[0] = rad[af][1];
-        p1.tap[1] = slot(af, 0), p1.rad[1] = rad[af][0];
-        col(if_first_pass<2>(dtype), p1, 1, af);
-    } else {
-        p1.out[0] = first_out;
-        p1.tap[0] = slot(af, 0), p1.rad[0] = rad[af][0];
-        col(if_first_pass<1>(dtype), p1, 1, af);
-    }
-    LAUNCHCHK();
-    record(h, 2);
-    if (!apply_in_2d) {  // the y pass of a 3-D filter
-        IfArgs p2 = base;
-        if (order) {  // S_y D_z, D_y S_z, S_y S_z
-            p2.in[0] = A, p2.in[1] = A + N;
-            p2.out[0] = B, p2.out[1] = B + N, p2.out[2] = B + 2 * N;
-            p2.tap[0] = slot(1, 0), p2.rad[0] = rad[1][0];
-            p2.tap[1] = slot(1, 1), p2.rad[1] = rad[1][1];
-            p2.tap[2] = slot(1, 0), p2.rad[2] = rad[1][0];
-            col(&k_if_col<float, 2, 3>, p2, 2, 1);
-        } else {
-            p2.in[0] = A;
-            p2.out[0] = B;
-            p2.tap[0] = slot(1, 0), p2.rad[0] = rad[1][0];
-            col(&k_if_col<float, 1, 1>, p2, 1, 1);
-        }
-        LAUNCHCHK();
-    }
-    record(h, 3);
-    {  // the x pass and the combination: the components in the order z, y, x
-        IfArgs p3 = base;
-        const int nin = order ? (apply_in_2d ? 2 : 3) : 1;
-        for (int s = 0; s < nin; ++s) {
-            p3.in[s] = B + (int64_t)s * N;
-            const int w = (order && s == nin - 1) ? 1 : 0;  // the last component is the x derivative
-            p3.tap[s] = slot(2, w), p3.rad[s] = rad[2][w];
-        }
-        p3.out[0] = dout;
-        p3.rmax = rmax[2];
-        p3.combine = filter_id;
-        const int64_t wgs = ((nz * ny + 3) / 4) * ((nx + kIfRowW - 1) / kIfRowW);
-        const size_t lds = sizeof(float) * 4 * (size_t)nin * (kIfRowW + 2 * p3.rmax);
-        const IfKernel k = nin == 1 ? &k_if_row<1> : nin == 2 ? &k_if_row<2> : &k_if_row<3>;
-        k<<<(unsigned)wgs, 256, lds, h->stream>>>(p3);
-        LAUNCHCHK();
-    }
-    record(h, 4);
-    if ((r = out_end(h, out, dout, fb, dev)) != CTWS_OK) return r;
-    stage_time(h, "if_minmax", 0, 1);
-    stage_time(h, "if_first", 1, 2);
-    stage_time(h, "if_y", 2, 3);
-    stage_time(h, "if_x", 3, 4);
-    return CTWS_OK;
-}
-}  // namespace
-}  // extern "C++"
-
-int ctws_filter_taps(double sigma, int order, double* out, int* radius) {
-    if (!radius || order < 0 || order > 2 || !if_sigma_ok(sigma)) return CTWS_EINVAL;
-    const std::vector<double> k = filter_taps(sigma, order);
-    *radius = (int)(k.size() / 2);
-    if (out) std::copy(k.begin(), k.end(), out);
-    return CTWS_OK;
-}
-
-int ctws_image_filter(ctws_handle* h, const void* data, int dtype, int64_t nz, int64_t ny, int64_t nx, int filter_id,
-                      const double sigma[3], int apply_in_2d, int normalize, float* out) {
-    return image_filter(h, data, dtype, nz, ny, nx, filter_id, sigma, apply_in_2d, normalize, out, false);
-}
-
-int ctws_image_filter_device(ctws_handle* h, const void* data, int dtype, int64_t nz, int64_t ny, int64_t nx,
-                             int filter_id, const double sigma[3], int apply_in_2d, int normalize, float* out) {
-    return image_filter(h, data, dtype, nz, ny, nx, filter_id, sigma, apply_in_2d, normalize, out, true);
-}
-
-// ---- RegionCentersWorkflow: the voxel farthest from the border per object (k_regcenter.hip) ---
-extern "C++" {
-namespace {
-// the larger boxes run in groups that share the two scratch arrays: voxels and objects per group
-// (a box above the voxel budget is a group of its own; the object budget is the grid's y limit)
-constexpr int64_t kRcGroupVox = 1ll << 28;
-constexpr int64_t kRcGroupObjs = 32768;
-
-// k_rc_col's tile width for a line of L voxels in a box nx wide: the power of two that covers nx,
-// at most 64, halved until the tile fits the LDS; 0 when a single column does not
-uint32_t rc_tile_width(int64_t L, int64_t nx) {
-    int64_t W = 1;
-    while (W < 64 && W < nx) W <<= 1;
-    while (W > 1 && L * W > kRcColWords) W >>= 1;
-    return L * W > kRcColWords ? 0u : (uint32_t)W;
-}
-
-int region_centers(ctws_handle* h, const uint64_t* labels, int64_t n_labels, int64_t k, const uint64_t* ids,
-                   const int64_t* offsets, const int64_t* shapes, const int64_t* pitches, const double* resolution,
-                   int64_t* centers, uint8_t* found, bool dev) {
-    int r;
-    if (!h) return CTWS_EINVAL;
-    if ((r = call_begin(h)) != CTWS_OK) return r;
-    if (n_labels < 0 || k < 0 || !resolution || (n_labels > 0 && !labels) ||
-        (k > 0 && (!ids || !offsets || !shapes || !pitches || !centers || !found))) {
-        h->err = "region centers: bad arguments (a label buffer, k objects with ids, offsets, shapes and pitches, "
-                 "a resolution, centres and flags)";
-        return CTWS_EINVAL;
-    }
-    if (k >= (1ll << 31)) {
-        h->err = "region centers: 2^31 or more objects in one call";
-        return CTWS_EUNSUPPORTED;
-    }
-    int64_t res[3];
-    for (int d = 0; d < 3; ++d) {
-        const double v = resolution[d];
-        if (!(v > 0.0) || !std::isfinite(v)) {
-            h->err = "region centers: a resolution that is not a positive number";
-            return CTWS_EINVAL;
-        }
-        if (v != std::floor(v) || v > 1024.0) {
-            h->err = "region centers: the resolution (" + std::to_string(resolution[0]) + ", " +
-                     std::to_string(resolution[1]) + ", " + std::to_string(resolution[2]) +
-                     ") is not three integers of at most 2^10.  The squared distances are exact integers only for "
-                     "integer resolutions; otherwise float64 roundings decide ties.  The centre does not change when "
-                     "all three values are scaled by a common factor: give [0.04, 0.004, 0.004] as [10, 1, 1]";
-            return CTWS_EUNSUPPORTED;
-        }
-        res[d] = (int64_t)v;
-    }
-    if (k == 0) return CTWS_OK;
-    std::vector<RcObj> objs((size_t)k);
-    std::vector<uint32_t> small, large;
-    for (int64_t i = 0; i < k; ++i) {
-        const int64_t* s = shapes + 3 * i;
-        const int64_t pz = pitches[2 * i], py = pitches[2 * i + 1];
-        RcObj& o = objs[(size_t)i];
-        o = RcObj{ids[i], offsets[i], pz, py, 0u, 0u, 0u, 0u, 0u, 0ull};
-        const std::string who = "region centers: object " + std::to_string(i) + " (id " + std::to_string(ids[i]) + ")";
-        if (s[0] < 0 || s[1] < 0 || s[2] < 0) {
-            h->err = who + ": a negative extent";
-            return CTWS_EINVAL;
-        }
-        if (s[0] == 0 || s[1] == 0 || s[2] == 0) continue;  // an empty box: not found
-        // sum_a (r_a n_a)^2 < 2^31: every r_a n_a is below 46341 first, so the squares cannot overflow
-        int64_t d2max = 0;
-        bool over = false;
-        for (int d = 0; d < 3; ++d) {
-            if (s[d] >= 46341 || res[d] * s[d] >= 46341) over = true;
-            else d2max += (res[d] * s[d]) * (res[d] * s[d]);
-        }
-        if (over || d2max >= (1ll << 31)) {
-            h->err = who + ": a box of " + std::to_string(s[0]) + " x " + std::to_string(s[1]) + " x " +
-                     std::to_string(s[2]) + " voxels at this resolution reaches a squared distance of 2^31 or more "
-                     "(the transform is 32-bit)";
-            return CTWS_EUNSUPPORTED;
-        }
-        const int64_t nvox = s[0] * s[1] * s[2];  // (each extent < 46341: no overflow)
-        if (nvox >= (1ll << 31)) {
-            h->err = who + ": 2^31 or more voxels in the box (the kernels index a box with 32 bits)";
-            return CTWS_EUNSUPPORTED;
-        }
-        const unsigned __int128 last = (unsigned __int128)(s[0] - 1) * (unsigned __int128)(pz < 0 ? 0 : pz) +
-                                       (unsigned __int128)(s[1] - 1) * (unsigned __int128)(py < 0 ? 0 : py) +
-                                       (unsigned __int128)s[2];
-        if (offsets[i] < 0 || py < s[2] || pz < 0 ||
-            (s[0] > 1 && (__int128)pz < (__int128)(s[1] - 1) * (__int128)py + (__int128)s[2]) ||
-            offsets[i] > n_labels || last > (unsigned __int128)(n_labels - offsets[i])) {
-            h->err = who + ": the box does not lie inside the label buffer (offset, pitches and extents)";
-            return CTWS_EINVAL;
-        }
-        o.nz = (uint32_t)s[0];
-        o.ny = (uint32_t)s[1];
-        o.nx = (uint32_t)s[2];
-        if (nvox <= kRcSmallVox) {
-            small.push_back((uint32_t)i);
-        } else {
-            o.wy = rc_tile_width(s[1], s[2]);
-            o.wz = rc_tile_width(s[0], s[2]);
-            large.push_back((uint32_t)i);
-        }
-    }
-    // the groups of the larger boxes and each box's place in the scratch arrays
-    struct Group {
-        size_t first, n;
-        int64_t vox;
-    };
-    std::vector<Group> groups;
-    int64_t scratch_vox = 0;
-    for (size_t j = 0; j < large.size(); ++j) {
-        RcObj& o = objs[large[j]];
-        const int64_t nvox = (int64_t)o.nz * o.ny * o.nx;
-        if (groups.empty() || groups.back().vox + nvox > kRcGroupVox || (int64_t)groups.back().n >= kRcGroupObjs)
-            groups.push_back(Group{j, 0, 0});
-        o.sbase = (uint64_t)groups.back().vox;
-        groups.back().n += 1;
-        groups.back().vox += nvox;
-        scratch_vox = std::max(scratch_vox, groups.back().vox);
-    }
-    const uint64_t* dl = labels;
-    if (n_labels > 0 && (r = stage_in(h, h->rc_lab, labels, sizeof(uint64_t) * (size_t)n_labels, dev, &dl)) != CTWS_OK)
-        return r;
-    const size_t ob = sizeof(RcObj) * (size_t)k, lb = sizeof(uint32_t) * (small.size() + large.size());
-    if ((r = grow(h, h->rc_objs, ob)) != CTWS_OK) return r;
-    if ((r = grow(h, h->rc_list, std::max<size_t>(lb, 4))) != CTWS_OK) return r;
-    if ((r = grow(h, h->rc_keys, sizeof(uint64_t) * (size_t)k)) != CTWS_OK) return r;
-    if ((r = grow(h, h->rc_a, sizeof(uint32_t) * (size_t)scratch_vox)) != CTWS_OK) return r;
-    if ((r = grow(h, h->rc_b, sizeof(uint32_t) * (size_t)scratch_vox)) != CTWS_OK) return r;
-    const RcObj* dobjs = (const RcObj*)h->rc_objs.p;
-    const uint32_t* dsmall = (const uint32_t*)h->rc_list.p;
-    const uint32_t* dlarge = dsmall + small.size();
-    unsigned long long* keys = (unsigned long long*)h->rc_keys.p;
-    uint32_t *ga = (uint32_t*)h->rc_a.p, *gb = (uint32_t*)h->rc_b.p;
-    long long* dcent;
-    uint8_t* dfound;
-    const size_t cb = 3 * sizeof(int64_t) * (size_t)k, fb = (size_t)k;
-    if ((r = out_begin(h, h->rc_cent, (long long*)centers, cb, dev, &dcent)) != CTWS_OK) return r;
-    if ((r = out_begin(h, h->rc_found, found, fb, dev, &dfound)) != CTWS_OK) return r;
-    // (the vectors live until the call's one wait in out_end)
-    HIPCHK(hipMemcpyAsync(h->rc_objs.p, objs.data(), ob, hipMemcpyHostToDevice, h->stream));
-    if (!small.empty())
-        HIPCHK(hipMemcpyAsync((void*)dsmall, small.data(), sizeof(uint32_t) * small.size(), hipMemcpyHostToDevice,
-                              h->stream));
-    if (!large.empty())
-        HIPCHK(hipMemcpyAsync((void*)dlarge, large.data(), sizeof(uint32_t) * large.size(), hipMemcpyHostToDevice,
-                              h->stream));
-    HIPCHK(hipMemsetAsync(keys, 0, sizeof(uint64_t) * (size_t)k, h->stream));
-    const RcRes rr = {(uint32_t)(res[0] * res[0]), (uint32_t)(res[1] * res[1]), (uint32_t)(res[2] * res[2])};
-    record(h, 0);
-    if (!small.empty()) {  // one launch serves all small objects of the call
-        k_rc_small<<<(unsigned)small.size(), kRcSmallThreads, 0, h->stream>>>(dl, dobjs, dsmall, rr, keys);
-        LAUNCHCHK();
-    }
-    record(h, 1);
-    for (const Group& g : groups) {
-        // the widest object of the group sizes the grid's x; every kernel strides over its own work
-        int64_t rows = 1, tiles_y = 1, tiles_z = 1, vox = 1;
-        bool staged_y = false, direct_y = false, staged_z = false, direct_z = false;
-        for (size_t j = g.first; j < g.first + g.n; ++j) {
-            const RcObj& o = objs[large[j]];
-            rows = std::max<int64_t>(rows, (int64_t)o.nz * o.ny);
-            vox = std::max<int64_t>(vox, (int64_t)o.nz * o.ny * o.nx);
-            if (o.wy) tiles_y = std::max<int64_t>(tiles_y, (int64_t)o.nz * ((o.nx + o.wy - 1) / o.wy));
-            if (o.wz) tiles_z = std::max<int64_t>(tiles_z, (int64_t)o.ny * ((o.nx + o.wz - 1) / o.wz));
-            (o.wy ? staged_y : direct_y) = true;
-            (o.wz ? staged_z : direct_z) = true;
-        }
-        const int64_t gcap = g.n > 64 ? 64 : 1024;  // many boxes fill the chip by their number
-        const unsigned gy = (unsigned)g.n;
-        const uint32_t* gl = dlarge + g.first;
-        const dim3 grows((unsigned)std::min<int64_t>((rows + 3) / 4, gcap), gy);
-        const dim3 gty((unsigned)std::min<int64_t>(tiles_y, gcap), gy), gtz((unsigned)std::min<int64_t>(tiles_z, gcap), gy);
-        const dim3 gdir((unsigned)std::min<int64_t>((vox + 255) / 256, gcap), gy);
-        k_rc_rows<<<grows, 256, 0, h->stream>>>(dl, dobjs, gl, rr, ga);
-        LAUNCHCHK();
-        if (staged_y) k_rc_col<true><<<gty, 256, 0, h->stream>>>(dobjs, gl, 1, rr.y2, 0, ga, gb, keys);
-        if (direct_y) k_rc_col<false><<<gdir, 256, 0, h->stream>>>(dobjs, gl, 1, rr.y2, 0, ga, gb, keys);
-        LAUNCHCHK();
-        if (staged_z) k_rc_col<true><<<gtz, 256, 0, h->stream>>>(dobjs, gl, 0, rr.z2, 1, gb, ga, keys);
-        if (direct_z) k_rc_col<false><<<gdir, 256, 0, h->stream>>>(dobjs, gl, 0, rr.z2, 1, gb, ga, keys);
-        LAUNCHCHK();
-    }
-    record(h, 2);
-    k_rc_finish<<<(unsigned)std::min<int64_t>((k + 255) / 256, 1024), 256, 0, h->stream>>>(dobjs, (uint32_t)k, keys, dcent,
-                                                                                          dfound);
-    LAUNCHCHK();
-    if (!dev) HIPCHK(copy_pieces(centers, dcent, cb, hipMemcpyDeviceToHost, h->stream));
-    if ((r = out_end(h, found, dfound, fb, dev)) != CTWS_OK) return r;
-    stage_time(h, "rc_small", 0, 1);
-    stage_time(h, "rc_large", 1, 2);
-    add_timing(h, "rc_small_objects", (float)small.size());  // (counts, as the flood's rounds)
-    add_timing(h, "rc_large_objects", (float)large.size());
-    add_timing(h, "rc_large_groups", (float)groups.size());
-    return CTWS_OK;
-}
-}  // namespace
-}  // extern "C++"
-
-int ctws_region_centers(ctws_handle* h, const uint64_t* labels, int64_t n_labels, int64_t k, const uint64_t* ids,
-                        const int64_t* offsets, const int64_t* shapes, const int64_t* pitches,
-                        const double resolution[3], int64_t* centers, uint8_t* found) {
-    return region_centers(h, labels, n_labels, k, ids, offsets, shapes, pitches, resolution, centers, found, false);
-}
-
-int ctws_region_centers_device(ctws_handle* h, const uint64_t* labels, int64_t n_labels, int64_t k, const uint64_t* ids,
-                               const int64_t* offsets, const int64_t* shapes, const int64_t* pitches,
-                               const double resolution[3], int64_t* centers, uint8_t* found) {
-    return region_centers(h, labels, n_labels, k, ids, offsets, shapes, pitches, resolution, centers, found, true);
-}
-
-// ---- EdgeFeaturesWorkflow: boundary-map statistics per edge (k_edgefeat.hip) ----------------
-extern "C++" {
-namespace {
-int edge_features_block(ctws_handle* h, const uint64_t* labels, const void* data, int data_dtype, int64_t nz,
-                        int64_t ny, int64_t nx, int64_t cz, int64_t cy, int64_t cx, int ignore_label,
-                        const uint64_t* nodes, int64_t n_nodes, const uint64_t* edges, int64_t n_edges, double* out,
-                        int64_t* n_missing, bool dev) {
-    int r;
-    if (!h) return CTWS_EINVAL;
-    if ((r = call_begin(h)) != CTWS_OK) return r;
-    if (n_missing) *n_missing = 0;
-    if (!labels || !data || nz <= 0 || ny <= 0 || nx <= 0 || cz <= 0 || cy <= 0 || cx <= 0 || cz > nz || cy > ny ||
-        cx > nx || n_nodes < 0 || n_edges < 0 || (n_edges > 0 && (!nodes || !edges || !out || n_nodes == 0))) {
-        h->err = "edge features: bad arguments (3-D boxes with 0 < core <= extended, tables for n_edges > 0)";
-        return CTWS_EINVAL;
-    }
-    if (data_dtype != CTWS_F32 && data_dtype != CTWS_U8) {
-        h->err = "edge features: the boundary map is float32 or uint8";
-        return CTWS_EUNSUPPORTED;
-    }
-    if (n_edges == 0) return CTWS_OK;  // nothing to accumulate into: no launch
-    r = check_extent(h, nz, ny, nx, "edge features", "block", "the sample kernel indexes a block with 32 bits");
-    if (r != CTWS_OK) return r;
-    if (n_nodes >= (1ll << 32) || n_edges >= (1ll << 32)) {
-        h->err = "edge features: 2^32 or more nodes or edges in one block";
-        return CTWS_EUNSUPPORTED;
-    }
-    const int64_t N = nz * ny * nx;
-    const size_t es = data_dtype == CTWS_U8 ? 1 : 4;
-    const uint64_t *dl, *dn, *de;
-    const void* dd;
-    double* dout;
-    const size_t out_bytes = 10 * sizeof(double) * (size_t)n_edges;
-    if ((r = stage_in(h, h->ef_lab, labels, sizeof(uint64_t) * (size_t)N, dev, &dl)) != CTWS_OK) return r;
-    if ((r = stage_in(h, h->ef_data, data, es * (size_t)N, dev, &dd)) != CTWS_OK) return r;
-    if ((r = stage_in(h, h->ef_nodes, nodes, sizeof(uint64_t) * (size_t)n_nodes, dev, &dn)) != CTWS_OK) return r;
-    if ((r = stage_in(h, h->ef_edges, edges, 2 * sizeof(uint64_t) * (size_t)n_edges, dev, &de)) != CTWS_OK) return r;
-    if ((r = out_begin(h, h->ef_out, out, out_bytes, dev, &dout)) != CTWS_OK) return r;
-    int b = 1;  // bits per rank
-    while ((1ll << b) < n_nodes) ++b;
-    int eb = 1;  // bits per edge index
-    while ((1ll << eb) < n_edges) ++eb;
-    if ((r = grow(h, h->ef_red, kRedWords * sizeof(uint64_t))) != CTWS_OK) return r;
-    if ((r = grow(h, h->ef_ekeys, sizeof(uint64_t) * (size_t)n_edges)) != CTWS_OK) return r;
-    unsigned long long* cnt = (unsigned long long*)h->ef_red.p;
-    HIPCHK(hipMemsetAsync(cnt, 0, kRedWords * sizeof(uint64_t), h->stream));
-    record(h, 0);
-    const unsigned ge = (unsigned)std::min<int64_t>((n_edges + 255) / 256, 8192);
-    k_ef_edge_keys<<<ge, 256, 0, h->stream>>>(de, n_edges, dn, n_nodes, b, (uint64_t*)h->ef_ekeys.p,
-                                              cnt + kRedBadEdges);
-    LAUNCHCHK();
-    record(h, 1);
-    EfArgs a;
-    a.lab = dl;
-    a.data = dd;
-    a.nz = (uint32_t)nz;
-    a.ny = (uint32_t)ny;
-    a.nx = (uint32_t)nx;
-    a.cz = (uint32_t)cz;
-    a.cy = (uint32_t)cy;
-    a.cx = (uint32_t)cx;
-    a.ignore = ignore_label ? 1 : 0;
-    a.tab = dn;
-    a.nt = (uint32_t)n_nodes;
-    a.b = b;
-    a.ekeys = (const uint64_t*)h->ef_ekeys.p;
-    a.ne = (uint32_t)n_edges;
-    a.count = cnt;
-    a.missing = cnt + kRedMissing;
-    const int64_t rows = cz * cy;
-    // the grid of k_rag_pairs: four workgroups per CU, every wave ends with an append of its own
-    const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>((rows + 3) / 4, 1024));
-    // first capacity: half a key per voxel (a block of fragments emits ~0.38).  The bad-edge
-    // count of k_ef_edge_keys is read with the pass's own counters, and not zeroed with them
-    EmitCap ecap = {kRedEmit, first_cap(N, 2)};
-    Emitted e;
-    r = counted_emit(
-        h, "edge features", cnt, kRedMissing + 1, kRedBadEdges + 1, &ecap, 1,
-        [&] {
-            const int r = grow(h, h->ef_keys, sizeof(uint64_t) * (size_t)ecap.cap);
-            if (r != CTWS_OK) return r;
-            a.keys = (uint64_t*)h->ef_keys.p;
-            a.cap = ecap.cap;
-            if (data_dtype == CTWS_U8) k_ef_samples<uint8_t><<<g, 256, 0, h->stream>>>(a);
-            else k_ef_samples<float><<<g, 256, 0, h->stream>>>(a);
-            return CTWS_OK;
-        },
-        [&](const unsigned long long* w) {
-            if (!w[kRedBadEdges]) return CTWS_OK;
-            h->err = "edge features: " + std::to_string(w[kRedBadEdges]) +
-                     " edges have an endpoint missing from the nodes or are not sorted and unique";
-            return CTWS_EINVAL;
-        },
-        &e);
-    if (r != CTWS_OK) return r;
-    record(h, 2);
-    const int64_t n = (int64_t)e.w[kRedEmit];
-    if (n >= (1ll << 31)) {
-        h->err = "edge features: 2^31 or more samples in one block";
-        return CTWS_EUNSUPPORTED;
-    }
-    if (n_missing) *n_missing = (int64_t)e.w[kRedMissing];
-    const uint64_t* sorted = (const uint64_t*)h->ef_keys.p;
-    if (n) {
-        size_t tb = 0;
-        HIPCHK(ef_sort(nullptr, tb, nullptr, nullptr, n, 32 + eb, h->stream));
-        if ((r = grow(h, h->ef_skeys, sizeof(uint64_t) * (size_t)n)) != CTWS_OK) return r;
-        if ((r = grow(h, h->ef_tmp, tb)) != CTWS_OK) return r;
-        HIPCHK(ef_sort(h->ef_tmp.p, tb, (const uint64_t*)h->ef_keys.p, (uint64_t*)h->ef_skeys.p, n, 32 + eb,
-                       h->stream));
-        sorted = (const uint64_t*)h->ef_skeys.p;
-    }
-    record(h, 3);
-    // one wave per edge, four per workgroup
-    k_ef_stats<<<(unsigned)((n_edges + 3) / 4), 256, 0, h->stream>>>(sorted, (uint32_t)n, (uint32_t)n_edges, dout);
-    LAUNCHCHK();
-    record(h, 4);
-    if ((r = out_end(h, out, dout, out_bytes, dev)) != CTWS_OK) return r;
-    stage_time(h, "ef_edge_keys", 0, 1);
-    stage_time(h, "ef_samples", 1, 2);
-    stage_time(h, "ef_sort", 2, 3);
-    stage_time(h, "ef_stats", 3, 4);
-    add_timing(h, "ef_sample_passes", (float)e.passes);
-    add_timing(h, "ef_keys", (float)n);
-    return CTWS_OK;
-}
-}  // namespace
-}  // extern "C++"
-
-int ctws_edge_features_block(ctws_handle* h, const uint64_t* labels, const void* data, int data_dtype, int64_t nz,
-                             int64_t ny, int64_t nx, int64_t cz, int64_t cy, int64_t cx, int ignore_label,
-                             const uint64_t* nodes, int64_t n_nodes, const uint64_t* edges, int64_t n_edges,
-                             double* out, int64_t* n_missing) {
-    return edge_features_block(h, labels, data, data_dtype, nz, ny, nx, cz, cy, cx, ignore_label, nodes, n_nodes,
-                               edges, n_edges, out, n_missing, false);
-}
-
-int ctws_edge_features_block_device(ctws_handle* h, const uint64_t* labels, const void* data, int data_dtype,
-                                    int64_t nz, int64_t ny, int64_t nx, int64_t cz, int64_t cy, int64_t cx,
-                                    int ignore_label, const uint64_t* nodes, int64_t n_nodes, const uint64_t* edges,
-                                    int64_t n_edges, double* out, int64_t* n_missing) {
-    return edge_features_block(h, labels, data, data_dtype, nz, ny, nx, cz, cy, cx, ignore_label, nodes, n_nodes,
-                               edges, n_edges, out, n_missing, true);
-}
-
-// ---- LiftedFeaturesFromNodeLabelsWorkflow: the sparse lifted neighbourhood (k_lifted.hip) ----
-extern "C++" {
-namespace {
-// The first capacity of the key buffer depends on the number of labelled nodes alone: 64 keys per
-// source (at depth 4 the 128^3 grid of the benchmark emits 19, a block's RAG 43), and never fewer than 2^16.
-constexpr int64_t kLfFirstCap = 1 << 16;
-constexpr int64_t kLfCapPerSource = 64;
-int64_t lf_first_cap(int64_t ns) { return std::max(kLfFirstCap, kLfCapPerSource * ns); }
-// Three workgroups of k_lf_bfs share a CU's LDS (54,272 B each); every wave owns a queue and a
-// bitmap over the n nodes (4 1/8 bytes per node), and the waves in flight are cut down to what fits
-// in this many bytes and in half of the free memory
-constexpr int kLfMaxGroups = 256 * 3;
-constexpr size_t kLfWaveBudget = (size_t)32 << 30;
-// the counter block: the row checks' three words, the sources, and a line for the append counter
-enum LfWord : size_t { kLfWordSources = 16, kLfWordEmit = 32, kLfWordVisits = 33, kLfWords = 48 };
-
-int lifted_neighborhood(ctws_handle* h, const uint64_t* edges, int64_t m, const uint64_t* labels, int64_t n, int depth,
-                        int mode, uint64_t ignore_label, uint64_t* out, int64_t cap, int64_t* n_out, bool dev) {
-    int r;
-    if (!h) return CTWS_EINVAL;
-    if ((r = call_begin(h)) != CTWS_OK) return r;
-    if (n_out) *n_out = 0;
-    if (!n_out || m < 0 || n < 0 || cap < 0 || (!out && cap > 0) || (m > 0 && !edges) || (n > 0 && !labels)) {
-        h->err = "lifted neighborhood: bad arguments (tables for n_edges > 0 and n_nodes > 0, out for cap > 0)";
-        return CTWS_EINVAL;
-    }
-    if (depth < 1) {
-        h->err = "lifted neighborhood: depth " + std::to_string(depth) + " (a lifted edge spans at least 2 hops; depth >= 1)";
-        return CTWS_EINVAL;
-    }
-    if (mode != CTWS_LIFTED_ALL && mode != CTWS_LIFTED_SAME && mode != CTWS_LIFTED_DIFFERENT) {
-        h->err = "lifted neighborhood: unknown mode " + std::to_string(mode) + " (0 all, 1 same, 2 different)";
-        return CTWS_EINVAL;
-    }
-    if (n >= (1ll << 32) || m >= (1ll << 31)) {
-        h->err = "lifted neighborhood: 2^32 or more nodes or 2^31 or more edges (ids and adjacency offsets are 32-bit)";
-        return CTWS_EUNSUPPORTED;
-    }
-    if (m == 0) return CTWS_OK;  // no edge, no path: no launch
-    if (n == 0) {
-        h->err = "lifted neighborhood: " + std::to_string(m) + " rows hold an id >= n_nodes (0)";
-        return CTWS_EINVAL;
-    }
-    const uint64_t *de, *dl;
-    if ((r = stage_in(h, h->lf_edges, edges, 2 * sizeof(uint64_t) * (size_t)m, dev, &de)) != CTWS_OK) return r;
-    if ((r = stage_in(h, h->lf_lab, labels, sizeof(uint64_t) * (size_t)n, dev, &dl)) != CTWS_OK) return r;
-    const size_t nb1 = sizeof(uint32_t) * ((size_t)n + 1);
-    if ((r = grow(h, h->lf_red, kLfWords * sizeof(uint64_t))) != CTWS_OK) return r;
-    if ((r = grow(h, h->lf_deg, nb1)) != CTWS_OK) return r;
-    if ((r = grow(h, h->lf_row, nb1)) != CTWS_OK) return r;
-    if ((r = grow(h, h->lf_adj, 2 * sizeof(uint32_t) * (size_t)m)) != CTWS_OK) return r;
-    if ((r = grow(h, h->lf_src, sizeof(uint32_t) * (size_t)n)) != CTWS_OK) return r;
-    unsigned long long* red = (unsigned long long*)h->lf_red.p;
-    uint32_t* deg = (uint32_t*)h->lf_deg.p;
-    uint32_t* row = (uint32_t*)h->lf_row.p;
-    // the rows' checks with the degrees, and the labelled nodes
-    HIPCHK(hipMemsetAsync(red, 0, kLfWords * sizeof(uint64_t), h->stream));
-    HIPCHK(hipMemsetAsync(deg, 0, nb1, h->stream));
-    record(h, 0);
-    const unsigned gm = (unsigned)std::min<int64_t>((m + 255) / 256, 8192);
-    const unsigned gn = (unsigned)std::min<int64_t>((n + 255) / 256, 8192);
-    k_lf_degrees<<<gm, 256, 0, h->stream>>>(de, (uint32_t)m, (uint64_t)n, deg, red);
-    k_lf_sources<<<gn, 256, 0, h->stream>>>(dl, (uint32_t)n, ignore_label, (uint32_t*)h->lf_src.p, red + kLfWordSources);
-    LAUNCHCHK();
-    unsigned long long w[kLfWordSources + 1];
-    HIPCHK(hipMemcpyAsync(w, red, sizeof(w), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (w[kLfBadId] || w[kLfBadUv] || w[kLfBadOrder]) {
-        h->err = "lifted neighborhood: the edge table is not a graph's: " + std::to_string(w[kLfBadId]) +
-                 " rows hold an id >= n_nodes (" + std::to_string(n) + "), " + std::to_string(w[kLfBadUv]) +
-                 " rows have u >= v, " + std::to_string(w[kLfBadOrder]) + " rows are not above their predecessor";
-        return CTWS_EINVAL;
-    }
-    const int64_t ns = (int64_t)w[kLfWordSources];
-    if (ns > n) {
-        h->err = "lifted neighborhood: the kernel counted " + std::to_string(ns) + " labelled nodes of " + std::to_string(n);
-        return CTWS_EHIP;
-    }
-    add_timing(h, "lf_sources", (float)ns);
-    if (ns == 0) return CTWS_OK;  // no labelled node: no search
-    // CSR of both directions
-    size_t tb_scan = 0;
-    HIPCHK(lf_scan(nullptr, tb_scan, nullptr, nullptr, n + 1, h->stream));
-    if ((r = grow(h, h->lf_tmp, tb_scan)) != CTWS_OK) return r;
-    HIPCHK(lf_scan(h->lf_tmp.p, tb_scan, deg, row, n + 1, h->stream));
-    HIPCHK(hipMemsetAsync(deg, 0, nb1, h->stream));  // (now the fill's cursors)
-    k_lf_fill<<<gm, 256, 0, h->stream>>>(de, (uint32_t)m, row, deg, (uint32_t*)h->lf_adj.p);
-    LAUNCHCHK();
-    record(h, 1);
-    // the waves in flight and their queues and bitmaps
-    const uint32_t qstride = (uint32_t)std::max<int64_t>(n - kLfQueueLds, 1);
-    const uint32_t bstride = (uint32_t)((n + 31) / 32);
-    const size_t wave_bytes = sizeof(uint32_t) * ((size_t)qstride + bstride);
-    int64_t groups = std::min<int64_t>((ns + kLfWaves - 1) / kLfWaves, kLfMaxGroups);
-    size_t free_bytes = 0, total_bytes = 0;
-    HIPCHK(hipMemGetInfo(&free_bytes, &total_bytes));
-    // (what the handle holds already is its own: a second call takes the waves of the first)
-    const size_t budget = std::max(h->lf_queue.bytes + h->lf_bits.bytes, std::min(kLfWaveBudget, free_bytes / 2));
-    groups = std::max<int64_t>(1, std::min<int64_t>(groups, (int64_t)(budget / wave_bytes) / kLfWaves));
-    const size_t nwaves = (size_t)groups * kLfWaves;
-    if ((r = grow(h, h->lf_queue, sizeof(uint32_t) * qstride * nwaves)) != CTWS_OK) return r;
-    if ((r = grow(h, h->lf_bits, sizeof(uint32_t) * bstride * nwaves)) != CTWS_OK) return r;
-    HIPCHK(hipMemsetAsync(h->lf_bits.p, 0, sizeof(uint32_t) * bstride * nwaves, h->stream));
-    int b = 1;  // bits per node id
-    while ((1ll << b) < n) ++b;
-    LfArgs a;
-    a.row = row;
-    a.adj = (const uint32_t*)h->lf_adj.p;
-    a.lab = dl;
-    a.src = (const uint32_t*)h->lf_src.p;
-    a.ns = (uint32_t)ns;
-    a.depth = (uint32_t)depth;
-    a.mode = mode;
-    a.ignore = ignore_label;
-    a.b = b;
-    a.queue = (uint32_t*)h->lf_queue.p;
-    a.qstride = qstride;
-    a.bits = (uint32_t*)h->lf_bits.p;
-    a.bstride = bstride;
-    a.count = red + kLfWordEmit;
-    a.visits = red + kLfWordVisits;
-    EmitCap ecap = {kRedEmit, (unsigned long long)lf_first_cap(ns)};
-    Emitted e;
-    r = counted_emit(
-        h, "lifted neighborhood", red + kLfWordEmit, 2, 2, &ecap, 1,
-        [&] {
-            const int r = grow(h, h->lf_keys, sizeof(uint64_t) * (size_t)ecap.cap);
-            if (r != CTWS_OK) return r;
-            a.keys = (uint64_t*)h->lf_keys.p;
-            a.cap = ecap.cap;
-            k_lf_bfs<<<(unsigned)groups, 64 * kLfWaves, 0, h->stream>>>(a);
-            return CTWS_OK;
-        },
-        [](const unsigned long long*) { return CTWS_OK; }, &e);
-    if (r != CTWS_OK) return r;
-    record(h, 2);
-    const unsigned long long k = e.w[kRedEmit];
-    add_timing(h, "lf_bfs_passes", (float)e.passes);
-    add_timing(h, "lf_keys", (float)k);
-    add_timing(h, "lf_visits", (float)e.w[1]);
-    add_timing(h, "lf_waves", (float)nwaves);
-    if (k >= (1ull << 31)) {
-        h->err = "lifted neighborhood: 2^31 or more lifted edges (" + std::to_string(k) + ") in one call";
-        return CTWS_EUNSUPPORTED;
-    }
-    *n_out = (int64_t)k;
-    if ((int64_t)k > cap) {
-        h->err = "lifted neighborhood: output capacity too small";
-        return CTWS_EINVAL;
-    }
-    if (k == 0) {
-        HIPCHK(hipStreamSynchronize(h->stream));
-        return CTWS_OK;
-    }
-    uint64_t* dout;
-    const size_t out_bytes = 2 * sizeof(uint64_t) * (size_t)k;
-    if ((r = out_begin(h, h->lf_out, out, out_bytes, dev, &dout)) != CTWS_OK) return r;
-    size_t tb_sort = 0;
-    HIPCHK(lf_sort(nullptr, tb_sort, nullptr, nullptr, (int64_t)k, 2 * b, h->stream));
-    if ((r = grow(h, h->lf_skeys, sizeof(uint64_t) * (size_t)k)) != CTWS_OK) return r;
-    if ((r = grow(h, h->lf_tmp, tb_sort)) != CTWS_OK) return r;
-    HIPCHK(lf_sort(h->lf_tmp.p, tb_sort, (const uint64_t*)h->lf_keys.p, (uint64_t*)h->lf_skeys.p, (int64_t)k, 2 * b,
-                   h->stream));
-    const unsigned gk = (unsigned)std::min<int64_t>(((int64_t)k + 255) / 256, 8192);
-    k_lf_unpack<<<gk, 256, 0, h->stream>>>((const uint64_t*)h->lf_skeys.p, (int64_t)k, b, dout);
-    LAUNCHCHK();
-    record(h, 3);
-    if ((r = out_end(h, out, dout, out_bytes, dev)) != CTWS_OK) return r;
-    stage_time(h, "lf_csr", 0, 1);
-    stage_time(h, "lf_bfs", 1, 2);
-    stage_time(h, "lf_sort", 2, 3);
-    return CTWS_OK;
-}
-}  // namespace
-}  // extern "C++"
-
-int ctws_lifted_neighborhood(ctws_handle* h, const uint64_t* edges, int64_t n_edges, const uint64_t* node_labels,
-                             int64_t n_nodes, int depth, int mode, uint64_t ignore_label, uint64_t* out, int64_t cap,
-                             int64_t* n_out) {
-    return lifted_neighborhood(h, edges, n_edges, node_labels, n_nodes, depth, mode, ignore_label, out, cap, n_out,
-                               false);
-}
-
-int ctws_lifted_neighborhood_device(ctws_handle* h, const uint64_t* edges, int64_t n_edges,
-                                    const uint64_t* node_labels, int64_t n_nodes, int depth, int mode,
-                                    uint64_t ignore_label, uint64_t* out, int64_t cap, int64_t* n_out) {
-    return lifted_neighborhood(h, edges, n_edges, node_labels, n_nodes, depth, mode, ignore_label, out, cap, n_out,
-                               true);
-}
-
-int ctws_lifted_limits(int64_t n_sources, int64_t* first_capacity, int64_t* visited_capacity) {
-    if (n_sources < 0) return CTWS_EINVAL;
-    if (first_capacity) *first_capacity = lf_first_cap(n_sources);
-    if (visited_capacity) *visited_capacity = kLfHashFill;
-    return CTWS_OK;
-}
-
-// ---- ConnectedComponentsWorkflow, SizeFilterAndGraphWatershedWorkflow: graph components and the
-// ---- seeded graph watershed over the merged graph's edge table (k_graphpost.hip) ----
-extern "C++" {
-namespace {
-// the counter block: the edge checks' words, and a line for a round's hooks and a pass's open flag
-enum GpWord : size_t { kGpWordHooks = 16, kGpWordOpen = 17, kGpWords = 32 };
-
-unsigned gp_grid(int64_t n) { return (unsigned)std::min<int64_t>((n + 255) / 256, 8192); }
-
-// the checks both calls share; *done: nothing is left to do (no node)
-int gp_begin(ctws_handle* h, const char* what, const void* edges, int64_t m, const void* nodes, int64_t n, const void* out,
-             bool* done) {
-    int r;
-    *done = false;
-    if ((r = call_begin(h)) != CTWS_OK) return r;
-    if (m < 0 || n < 0 || (m > 0 && !edges) || (n > 0 && (!nodes || !out))) {
-        h->err = std::string(what) + ": bad arguments (an edge table for n_edges > 0, node arrays for n_nodes > 0)";
-        return CTWS_EINVAL;
-    }
-    if (n >= (1ll << 32) || m >= (1ll << 32)) {
-        h->err = std::string(what) + ": 2^32 or more nodes or edges (node ids and edge ranks are 32-bit)";
-        return CTWS_EUNSUPPORTED;
-    }
-    if (n == 0) {
-        if (m > 0) {
-            h->err = std::string(what) + ": " + std::to_string(m) + " rows hold an id >= n_nodes (0)";
-            return CTWS_EINVAL;
-        }
-        *done = true;
-    }
-    return CTWS_OK;
-}
-
-// the edge checks' counters of a call; the stream has drained when this returns
-int gp_edge_check(ctws_handle* h, const char* what, unsigned long long* red, int64_t n) {
-    unsigned long long w[2];
-    HIPCHK(hipMemcpyAsync(w, red, sizeof(w), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (w[kGpBadId] || w[kGpBadNan]) {
-        h->err = std::string(what) + ": " + std::to_string(w[kGpBadId]) + " rows hold an id >= n_nodes (" +
-                 std::to_string(n) + "), " + std::to_string(w[kGpBadNan]) + " weights are NaN";
-        return CTWS_EINVAL;
-    }
-    return CTWS_OK;
-}
-
-// lab (n, on the device) renumbered in place by first appearance over the index, from 1, zeros kept
-int gp_relabel(ctws_handle* h, uint64_t* lab, int64_t n) {
-    int r;
-    if ((r = grow(h, h->gp_keys, sizeof(uint64_t) * (size_t)n)) != CTWS_OK) return r;
-    if ((r = grow(h, h->gp_skeys, sizeof(uint64_t) * (size_t)n)) != CTWS_OK) return r;
-    if ((r = grow(h, h->gp_idx, sizeof(uint32_t) * (size_t)n)) != CTWS_OK) return r;
-    if ((r = grow(h, h->gp_sidx, sizeof(uint32_t) * (size_t)n)) != CTWS_OK) return r;
-    if ((r = grow(h, h->gp_best, sizeof(uint32_t) * (size_t)n)) != CTWS_OK) return r;
-    if ((r = grow(h, h->gp_num, sizeof(uint32_t) * (size_t)n)) != CTWS_OK) return r;
-    size_t tb_sort = 0, tb_scan = 0;
-    HIPCHK(gp_sort(nullptr, tb_sort, nullptr, nullptr, nullptr, nullptr, n, h->stream));
-    HIPCHK(gp_scan(nullptr, tb_scan, nullptr, nullptr, n, h->stream));
-    if ((r = grow(h, h->gp_tmp, std::max(tb_sort, tb_scan))) != CTWS_OK) return r;
-    uint64_t *keys = (uint64_t*)h->gp_keys.p, *skeys = (uint64_t*)h->gp_skeys.p;
-    uint32_t *idx = (uint32_t*)h->gp_idx.p, *sidx = (uint32_t*)h->gp_sidx.p;
-    uint32_t *flag = (uint32_t*)h->gp_best.p, *num = (uint32_t*)h->gp_num.p;
-    const unsigned gn = gp_grid(n);
-    k_gp_rl_keys<<<gn, 256, 0, h->stream>>>(lab, (uint64_t)n, keys, idx, flag);
-    HIPCHK(gp_sort(h->gp_tmp.p, tb_sort, keys, skeys, idx, sidx, n, h->stream));
-    k_gp_rl_heads<<<gn, 256, 0, h->stream>>>(skeys, sidx, (uint64_t)n, flag);
-    HIPCHK(gp_scan(h->gp_tmp.p, tb_scan, flag, num, n, h->stream));
-    k_gp_rl_write<<<gn, 256, 0, h->stream>>>(skeys, sidx, num, (uint64_t)n, lab);
-    LAUNCHCHK();
-    return CTWS_OK;
-}
-
-int graph_components(ctws_handle* h, const uint64_t* edges, int64_t m, const uint64_t* assignments, int64_t n,
-                     uint64_t* out, bool dev) {
-    const char* what = "graph components";
-    int r;
-    bool done;
-    if (!h) return CTWS_EINVAL;
-    if ((r = gp_begin(h, what, edges, m, assignments, n, out, &done)) != CTWS_OK || done) return r;
-    const uint64_t *de = nullptr, *da;
-    if (m > 0 && (r = stage_in(h, h->gp_edges, edges, 2 * sizeof(uint64_t) * (size_t)m, dev, &de)) != CTWS_OK) return r;
-    if ((r = stage_in(h, h->gp_in, assignments, sizeof(uint64_t) * (size_t)n, dev, &da)) != CTWS_OK) return r;
-    const size_t nb = sizeof(uint32_t) * (size_t)n;
-    if ((r = grow(h, h->gp_red, kGpWords * sizeof(uint64_t))) != CTWS_OK) return r;
-    if ((r = grow(h, h->gp_parent, nb)) != CTWS_OK) return r;
-    if ((r = grow(h, h->gp_best, nb)) != CTWS_OK) return r;
-    if ((r = grow(h, h->gp_num, nb)) != CTWS_OK) return r;
-    size_t tb_scan = 0;
-    HIPCHK(gp_scan(nullptr, tb_scan, nullptr, nullptr, n, h->stream));
-    if ((r = grow(h, h->gp_tmp, tb_scan)) != CTWS_OK) return r;
-    unsigned long long* red = (unsigned long long*)h->gp_red.p;
-    uint32_t *parent = (uint32_t*)h->gp_parent.p, *flag = (uint32_t*)h->gp_best.p, *num = (uint32_t*)h->gp_num.p;
-    const unsigned gn = gp_grid(n);
-    record(h, 0);
-    k_gp_init<<<gn, 256, 0, h->stream>>>(parent, nullptr, (uint64_t)n);
-    if (m > 0) {  // (no edge: no edge kernel, every labelled node is a component)
-        HIPCHK(hipMemsetAsync(red, 0, kGpWords * sizeof(uint64_t), h->stream));
-        k_gp_union<<<gp_grid(m), 256, 0, h->stream>>>(de, (uint64_t)m, (uint64_t)n, da, parent, red);
-        LAUNCHCHK();
-        if ((r = gp_edge_check(h, what, red, n)) != CTWS_OK) return r;  // (before anything is written to out)
-        k_gp_compress<<<gn, 256, 0, h->stream>>>(parent, (uint64_t)n);
-    }
-    record(h, 1);
-    uint64_t* dout;
-    const size_t out_bytes = sizeof(uint64_t) * (size_t)n;
-    if ((r = out_begin(h, h->gp_out, out, out_bytes, dev, &dout)) != CTWS_OK) return r;
-    k_gp_cc_flag<<<gn, 256, 0, h->stream>>>(parent, da, (uint64_t)n, flag);
-    HIPCHK(gp_scan(h->gp_tmp.p, tb_scan, flag, num, n, h->stream));
-    k_gp_cc_write<<<gn, 256, 0, h->stream>>>(parent, da, num, (uint64_t)n, dout);
-    LAUNCHCHK();
-    record(h, 2);
-    if ((r = out_end(h, out, dout, out_bytes, dev)) != CTWS_OK) return r;
-    stage_time(h, "gc_union", 0, 1);
-    stage_time(h, "gc_number", 1, 2);
-    return CTWS_OK;
-}
-
-int graph_watershed(ctws_handle* h, const uint64_t* edges, const double* weights, int64_t m, const uint64_t* seeds,
-                    int64_t n, int relabel, uint64_t* out, bool dev) {
-    const char* what = "graph watershed";
-    int r;
-    bool done;
-    if (!h) return CTWS_EINVAL;
-    if ((r = gp_begin(h, what, edges, m, seeds, n, out, &done)) != CTWS_OK || done) return r;
-    if (m > 0 && !weights) {
-        h->err = "graph watershed: bad arguments (a weight per edge for n_edges > 0)";
-        return CTWS_EINVAL;
-    }
-    if ((const void*)out == (const void*)seeds) {
-        h->err = "graph watershed: out is the seed array (a node reads its root's seed while others are written)";
-        return CTWS_EINVAL;
-    }
-    const uint64_t *de, *ds;
-    const double* dw;
-    if ((r = stage_in(h, h->gp_in, seeds, sizeof(uint64_t) * (size_t)n, dev, &ds)) != CTWS_OK) return r;
-    uint64_t* dout;
-    const size_t out_bytes = sizeof(uint64_t) * (size_t)n;
-    if ((r = out_begin(h, h->gp_out, out, out_bytes, dev, &dout)) != CTWS_OK) return r;
-    const unsigned gn = gp_grid(n);
-    int rounds = 0, passes = 0;
-    record(h, 0);
-    if (m == 0) {  // no edge: no edge kernel, the seeds are the result
-        if (dout != ds) HIPCHK(hipMemcpyAsync(dout, ds, out_bytes, hipMemcpyDeviceToDevice, h->stream));
-        record(h, 1);
-        record(h, 2);
-    } else {
-        if ((r = stage_in(h, h->gp_edges, edges, 2 * sizeof(uint64_t) * (size_t)m, dev, &de)) != CTWS_OK) return r;
-        if ((r = stage_in(h, h->gp_w, weights, sizeof(double) * (size_t)m, dev, &dw)) != CTWS_OK) return r;
-        const size_t nb = sizeof(uint32_t) * (size_t)n, mb = sizeof(uint32_t) * (size_t)m;
-        if ((r = grow(h, h->gp_red, kGpWords * sizeof(uint64_t))) != CTWS_OK) return r;
-        if ((r = grow(h, h->gp_parent, nb)) != CTWS_OK) return r;
-        if ((r = grow(h, h->gp_next, nb)) != CTWS_OK) return r;
-        if ((r = grow(h, h->gp_best, nb)) != CTWS_OK) return r;
-        if ((r = grow(h, h->gp_su, mb)) != CTWS_OK) return r;
-        if ((r = grow(h, h->gp_sv, mb)) != CTWS_OK) return r;
-        if ((r = grow(h, h->gp_idx, mb)) != CTWS_OK) return r;
-        if ((r = grow(h, h->gp_sidx, mb)) != CTWS_OK) return r;
-        if ((r = grow(h, h->gp_keys, 2 * mb)) != CTWS_OK) return r;
-        if ((r = grow(h, h->gp_skeys, 2 * mb)) != CTWS_OK) return r;
-        size_t tb_sort = 0;
-        HIPCHK(gp_sort(nullptr, tb_sort, nullptr, nullptr, nullptr, nullptr, m, h->stream));
-        if ((r = grow(h, h->gp_tmp, tb_sort)) != CTWS_OK) return r;
-        unsigned long long* red = (unsigned long long*)h->gp_red.p;
-        uint32_t *parent = (uint32_t*)h->gp_parent.p, *next = (uint32_t*)h->gp_next.p, *best = (uint32_t*)h->gp_best.p;
-        uint32_t *su = (uint32_t*)h->gp_su.p, *sv = (uint32_t*)h->gp_sv.p;
-        const unsigned gm = gp_grid(m);
-        // the checks and the ranks: one stable sort of (ordered weight, edge index)
-        HIPCHK(hipMemsetAsync(red, 0, kGpWords * sizeof(uint64_t), h->stream));
-        k_gp_keys<<<gm, 256, 0, h->stream>>>(de, dw, (uint64_t)m, (uint64_t)n, (uint64_t*)h->gp_keys.p,
-                                             (uint32_t*)h->gp_idx.p, red);
-        LAUNCHCHK();
-        if ((r = gp_edge_check(h, what, red, n)) != CTWS_OK) return r;
-        HIPCHK(gp_sort(h->gp_tmp.p, tb_sort, (const uint64_t*)h->gp_keys.p, (uint64_t*)h->gp_skeys.p,
-                       (const uint32_t*)h->gp_idx.p, (uint32_t*)h->gp_sidx.p, m, h->stream));
-        k_gp_sorted_ends<<<gm, 256, 0, h->stream>>>(de, (const uint32_t*)h->gp_sidx.p, (uint64_t)m, su, sv);
-        k_gp_init<<<gn, 256, 0, h->stream>>>(parent, best, (uint64_t)n);
-        LAUNCHCHK();
-        record(h, 1);
-        // the rounds: both loops are capped here, and a cap that is reached is an error
-        bool fixed = false;
-        unsigned long long w[2];
-        for (int round = 0; round < kGpMaxIters && !fixed; ++round) {
-            HIPCHK(hipMemsetAsync(red + kGpWordHooks, 0, 2 * sizeof(uint64_t), h->stream));
-            k_gp_offer<<<gm, 256, 0, h->stream>>>(su, sv, (uint64_t)m, parent, ds, best);
-            k_gp_hook<<<gn, 256, 0, h->stream>>>(su, sv, parent, ds, best, next, (uint64_t)n, red + kGpWordHooks);
-            k_gp_jump<<<gn, 256, 0, h->stream>>>(next, best, (uint64_t)n, red + kGpWordOpen);
-            LAUNCHCHK();
-            HIPCHK(hipMemcpyAsync(w, red + kGpWordHooks, sizeof(w), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipStreamSynchronize(h->stream));
-            if (w[0] == 0ull) {  // no component hooked: next is parent, the forest is final
-                fixed = true;
-                break;
-            }
-            ++rounds;
-            int p = 1;
-            for (; w[1] != 0ull && p < kGpMaxIters; ++p) {
-                HIPCHK(hipMemsetAsync(red + kGpWordOpen, 0, sizeof(uint64_t), h->stream));
-                k_gp_jump<<<gn, 256, 0, h->stream>>>(next, nullptr, (uint64_t)n, red + kGpWordOpen);
-                LAUNCHCHK();
-                HIPCHK(hipMemcpyAsync(w + 1, red + kGpWordOpen, sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-                HIPCHK(hipStreamSynchronize(h->stream));
-            }
-            passes += p;
-            if (w[1] != 0ull) {
-                h->err = "graph watershed: pointer jumping did not reach a fixpoint in " + std::to_string(kGpMaxIters) +
-                         " passes (round " + std::to_string(round) + ")";
-                return CTWS_EHIP;
-            }
-            std::swap(parent, next);
-        }
-        if (!fixed) {
-            h->err = "graph watershed: components still hooked after " + std::to_string(kGpMaxIters) + " rounds";
-            return CTWS_EHIP;
-        }
-        record(h, 2);
-        k_gp_ws_write<<<gn, 256, 0, h->stream>>>(parent, ds, (uint64_t)n, dout);
-        LAUNCHCHK();
-    }
-    if (relabel && (r = gp_relabel(h, dout, n)) != CTWS_OK) return r;
-    record(h, 3);
-    if ((r = out_end(h, out, dout, out_bytes, dev)) != CTWS_OK) return r;
-    stage_time(h, "gw_sort", 0, 1);
-    stage_time(h, "gw_rounds_ms", 1, 2);
-    stage_time(h, "gw_write", 2, 3);
-    add_timing(h, "gw_rounds", (float)rounds);
-    add_timing(h, "gw_jump_passes", (float)passes);
-    return CTWS_OK;
-}
-}  // namespace
-}  // extern "C++"
-
-int ctws_graph_components(ctws_handle* h, const uint64_t* edges, int64_t n_edges, const uint64_t* assignments,
-                          int64_t n_nodes, uint64_t* out) {
-    return graph_components(h, edges, n_edges, assignments, n_nodes, out, false);
-}
-
-int ctws_graph_components_device(ctws_handle* h, const uint64_t* edges, int64_t n_edges, const uint64_t* assignments,
-                                 int64_t n_nodes, uint64_t* out) {
-    return graph_components(h, edges, n_edges, assignments, n_nodes, out, true);
-}
-
-int ctws_graph_watershed(ctws_handle* h, const uint64_t* edges, const double* weights, int64_t n_edges,
-                         const uint64_t* seeds, int64_t n_nodes, int relabel, uint64_t* out) {
-    return graph_watershed(h, edges, weights, n_edges, seeds, n_nodes, relabel, out, false);
-}
-
-int ctws_graph_watershed_device(ctws_handle* h, const uint64_t* edges, const double* weights, int64_t n_edges,
-                                const uint64_t* seeds, int64_t n_nodes, int relabel, uint64_t* out) {
-    return graph_watershed(h, edges, weights, n_edges, seeds, n_nodes, relabel, out, true);
-}
-
-// ---- ThresholdedComponentsWorkflow: BlockComponents (k_threshcc.hip) -----------------------
-extern "C++" {
-namespace {
-size_t tc_dtype_size(int dt) {
-    switch (dt) {
-        case CTWS_U8: case CTWS_I8: return 1;
-        case CTWS_U16: case CTWS_I16: return 2;
-        case CTWS_F32: case CTWS_I32: case CTWS_U32: return 4;
-        case CTWS_F64: case CTWS_I64: case CTWS_U64: return 8;
-        default: return 0;
-    }
-}
-// dispatch a k_tc_* template over the dataset dtype (float32 is the caller's own case)
-template <class F>
-void tc_dispatch(int dt, F f) {
-    switch (dt) {
-        case CTWS_U8: f((const uint8_t*)nullptr); break;
-        case CTWS_I8: f((const int8_t*)nullptr); break;
-        case CTWS_U16: f((const uint16_t*)nullptr); break;
-        case CTWS_I16: f((const int16_t*)nullptr); break;
-        case CTWS_U32: f((const uint32_t*)nullptr); break;
-        case CTWS_I32: f((const int32_t*)nullptr); break;
-        case CTWS_U64: f((const uint64_t*)nullptr); break;
-        case CTWS_I64: f((const int64_t*)nullptr); break;
-        case CTWS_F64: f((const double*)nullptr); break;
-        default: break;
-    }
-}
-}  // namespace
-}  // extern "C++"
-
-int ctws_threshold_components(ctws_handle* h, const float* input, const uint8_t* mask, int64_t nz, int64_t ny,
-                              int64_t nx, int on_device, int mode, double threshold, int normalize, uint64_t* out,
-                              int64_t* n_labels) {
-    return ctws_threshold_components_ex(h, input, CTWS_F32, mask, nz, ny, nx, on_device, mode, threshold, normalize,
-                                        0.0, out, n_labels);
-}
-
-int ctws_threshold_components_ex(ctws_handle* h, const void* input, int dtype, const uint8_t* mask, int64_t nz,
-                                 int64_t ny, int64_t nx, int on_device, int mode, double threshold, int normalize,
-                                 double sigma, uint64_t* out, int64_t* n_labels) {
-    if (!h || !n_labels || nz < 0 || ny < 0 || nx < 0 || mode < 0 || mode > 2 || !(sigma >= 0.0)) return CTWS_EINVAL;
-    const size_t esz = tc_dtype_size(dtype);
-    if (!esz) {
-        h->err = "ctws_threshold_components_ex: unsupported dtype";
-        return CTWS_EINVAL;
-    }
-    const int64_t n = nz * ny * nx;
-    if ((!input || !out) && n > 0) return CTWS_EINVAL;
-    h->err.clear();
-    HIPCHK(hipSetDevice(h->device));
-    *n_labels = 0;
-    if (n == 0) return CTWS_OK;
-    if (n >= (int64_t)kNoParent || nz > INT32_MAX || ny > INT32_MAX || nx > INT32_MAX) {
-        h->err = "ctws_threshold_components: block too large (needs < 2^32 - 1 voxels)";
-        return CTWS_EINVAL;
-    }
-    std::vector<double> taps;
-    if (sigma > 0.0) {
-        taps = gaussian_taps(sigma);
-        const int64_t rad = (int64_t)taps.size() / 2;
-        if (nz < rad + 1 || ny < rad + 1 || nx < rad + 1) {  // vigra: "kernel longer than line"
-            h->err = "ctws_threshold_components_ex: block shorter than the Gaussian radius + 1 along an axis";
-            return CTWS_EINVAL;
-        }
-    }
-    int r;
-    const void* dsrc = input;
-    const uint8_t* dmask = mask;
-    uint64_t* dout = out;
-    if (!on_device) {
-        if ((r = grow(h, h->tc_raw, esz * (size_t)n)) != CTWS_OK) return r;
-        if ((r = grow(h, h->tc_out, sizeof(uint64_t) * (size_t)n)) != CTWS_OK) return r;
-        HIPCHK(hipMemcpyAsync(h->tc_raw.p, input, esz * (size_t)n, hipMemcpyHostToDevice, h->stream));
-        dsrc = h->tc_raw.p;
-        dout = (uint64_t*)h->tc_out.p;
-        if (mask) {
-            if ((r = grow(h, h->tc_mask, (size_t)n)) != CTWS_OK) return r;
-            HIPCHK(hipMemcpyAsync(h->tc_mask.p, mask, (size_t)n, hipMemcpyHostToDevice, h->stream));
-            dmask = (const uint8_t*)h->tc_mask.p;
-        }
-    }
-    const int64_t nw = (n + 63) / 64, nc = (nw + 255) / 256;
-    if ((r = grow(h, h->tc_P, sizeof(uint32_t) * (size_t)n)) != CTWS_OK) return r;
-    if ((r = grow(h, h->tc_bits, sizeof(uint64_t) * (size_t)nw)) != CTWS_OK) return r;
-    if ((r = grow(h, h->tc_cnt, sizeof(uint32_t) * (size_t)nc)) != CTWS_OK) return r;
-    if ((r = grow(h, h->tc_offs, sizeof(uint64_t) * (size_t)(nc + 1))) != CTWS_OK) return r;
-    if ((r = grow(h, h->tc_woff, sizeof(uint32_t) * (size_t)nw)) != CTWS_OK) return r;
-    if ((r = grow(h, h->tc_red, 4 * sizeof(uint32_t))) != CTWS_OK) return r;
-    uint32_t* red = (uint32_t*)h->tc_red.p;  // [0] min, [1] max (ordered float bits), [2] any member
-    const uint32_t init[3] = {0xFFFFFFFFu, 0u, 0u};
-    HIPCHK(hipMemcpyAsync(red, init, sizeof(init), hipMemcpyHostToDevice, h->stream));
-    const unsigned gs = (unsigned)std::min<int64_t>((n + 255) / 256, 8192);  // grid of the streaming passes
-    const unsigned gm = (unsigned)std::min<int64_t>((n + 4095) / 4096, 256);  // k_tc_minmax
-    TcParams p;
-    p.nz = (int)nz;
-    p.ny = (int)ny;
-    p.nx = (int)nx;
-    p.mode = mode;
-    p.normalize = normalize ? 1 : 0;
-    p.thr = (float)threshold;
-    const float* din = (const float*)dsrc;  // the float32 values k_tc_tile thresholds
-    const bool raw_cmp = !normalize && sigma == 0.0 && dtype != CTWS_F32;
-    if (raw_cmp || dtype != CTWS_F32) {
-        if ((r = grow(h, h->tc_in, sizeof(float) * (size_t)n)) != CTWS_OK) return r;
-        float* f = (float*)h->tc_in.p;
-        if (raw_cmp) {
-            // numpy's float64 comparison of the raw values; k_tc_tile tests the 0 / 1 result
-            tc_dispatch(dtype, [&](auto tp) {
-                using T = std::remove_cv_t<std::remove_pointer_t<decltype(tp)>>;
-                k_tc_raw_members<T><<<gs, 256, 0, h->stream>>>((const T*)dsrc, n, mode, threshold, f);
-            });
-            p.mode = 0;
-            p.thr = 0.5f;
-        } else {
-            tc_dispatch(dtype, [&](auto tp) {
-                using T = std::remove_cv_t<std::remove_pointer_t<decltype(tp)>>;
-                k_tc_to_f32<T><<<gs, 256, 0, h->stream>>>((const T*)dsrc, n, f);
-            });
-        }
-        LAUNCHCHK();
-        din = f;
-    }
-    if (sigma > 0.0) {
-        // x (float32) -> [normalize] -> Gaussian z, y, x -> normalized by k_tc_tile
-        if ((r = grow(h, h->tc_tmp, sizeof(float) * (size_t)n)) != CTWS_OK) return r;
-        if ((r = grow(h, h->tc_taps, sizeof(double) * taps.size())) != CTWS_OK) return r;
-        if (din == (const float*)dsrc) {  // float32 input: work on a copy, the caller's buffer is const
-            if ((r = grow(h, h->tc_in, sizeof(float) * (size_t)n)) != CTWS_OK) return r;
-            HIPCHK(hipMemcpyAsync(h->tc_in.p, din, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice, h->stream));
-            din = (const float*)h->tc_in.p;
-        }
-        float* a = (float*)h->tc_in.p;
-        float* b = (float*)h->tc_tmp.p;
-        if (normalize) {
-            k_tc_minmax<<<gm, 256, 0, h->stream>>>(a, n, red);
-            k_tc_normalize<<<gs, 256, 0, h->stream>>>(a, n, red);
-            HIPCHK(hipMemcpyAsync(red, init, sizeof(init), hipMemcpyHostToDevice, h->stream));
-        }
-        // (pageable upload: the host vector is gone after this call returns, the copy is not)
-        HIPCHK(hipMemcpy(h->tc_taps.p, taps.data(), sizeof(double) * taps.size(), hipMemcpyHostToDevice));
-        const int rad = (int)taps.size() / 2;
-        for (int axis = 0; axis < 3; ++axis) {
-            k_tc_gauss<<<gs, 256, 0, h->stream>>>(a, b, (int)nz, (int)ny, (int)nx, axis,
-                                                  (const double*)h->tc_taps.p, rad);
-            std::swap(a, b);
-        }
-        LAUNCHCHK();
-        din = a;
-        p.normalize = 1;  // vu.normalize of the smoothed block
-    }
-    if (p.normalize) {
-        if (reinterpret_cast<uintptr_t>(din) % 16 != 0) {
-            h->err = "ctws_threshold_components: input not 16-byte aligned";
-            return CTWS_EINVAL;
-        }
-        k_tc_minmax<<<gm, 256, 0, h->stream>>>(din, n, red);
-    }
-    const int64_t tiles = ((nx + 63) / 64) * ((ny + 7) / 8) * ((nz + 7) / 8);
-    uint32_t* P = (uint32_t*)h->tc_P.p;
-    k_tc_tile<<<(unsigned)tiles, 256, 0, h->stream>>>(din, dmask, p, red, P, red + 2);
-    LAUNCHCHK();
-    uint32_t any = 0;
-    HIPCHK(hipMemcpyAsync(&any, red + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (!any) return CTWS_OK;  // an empty block: no labels, the output is not written
-    k_tc_merge<<<(unsigned)std::min<int64_t>(tiles, 4096), 256, 0, h->stream>>>(p, P);
-    const unsigned gv = (unsigned)((n + 255) / 256);
-    k_tc_roots<<<gv, 256, 0, h->stream>>>(P, n, (uint64_t*)h->tc_bits.p);
-    k_bits_chunk_count<<<(unsigned)nc, 256, 0, h->stream>>>((const uint64_t*)h->tc_bits.p, nw,
-                                                           (uint32_t*)h->tc_cnt.p);
-    k_scan_chunks<<<1, 256, 0, h->stream>>>((const uint32_t*)h->tc_cnt.p, nc, (uint64_t*)h->tc_offs.p);
-    k_tc_wordoff<<<(unsigned)nc, 256, 0, h->stream>>>((const uint64_t*)h->tc_bits.p, nw,
-                                                     (const uint64_t*)h->tc_offs.p, (uint32_t*)h->tc_woff.p);
-    k_tc_label<<<gv, 256, 0, h->stream>>>(P, n, (const uint64_t*)h->tc_bits.p, (const uint32_t*)h->tc_woff.p, dout);
-    LAUNCHCHK();
-    uint64_t total = 0;
-    HIPCHK(hipMemcpyAsync(&total, (uint64_t*)h->tc_offs.p + nc, sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-    if (!on_device) HIPCHK(hipMemcpyAsync(out, dout, sizeof(uint64_t) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    *n_labels = (int64_t)total;
-    return CTWS_OK;
-}
-
-
-// ---- ThresholdedComponentsWorkflow: MergeAssignments (host) --------------------------------
-// nifty.ufd.boost_ufd(n).merge(pairs); find(arange(n)) (merge_assignments.py:125-130): boost's
-// disjoint_sets with union by rank -- link(find(a), find(b)) puts the root of lower rank under
-// the other and, at equal ranks, the first root under the second (whose rank grows).  The
-// representatives depend on the merge order, so this stays a sequential pass over the pairs.
-int ctws_ufd_find(int64_t n, const uint64_t* pairs, int64_t n_pairs, uint64_t* out) {
-    if (n < 0 || n_pairs < 0 || (!out && n > 0) || (!pairs && n_pairs > 0)) return CTWS_EINVAL;
-    std::vector<uint64_t> parent((size_t)n);
-    std::vector<uint8_t> rank((size_t)n, 0);
-    for (int64_t i = 0; i < n; ++i) parent[(size_t)i] = (uint64_t)i;
-    auto find = [&](uint64_t a) {
-        uint64_t r = a;
-        while (parent[r] != r) r = parent[r];
-        while (parent[a] != r) {  // full path compression (boost's default find)
-            const uint64_t nx = parent[a];
-            parent[a] = r;
-            a = nx;
-        }
-        return r;
-    };
-    for (int64_t k = 0; k < n_pairs; ++k) {
-        const uint64_t a = pairs[2 * k], b = pairs[2 * k + 1];
-        if (a >= (uint64_t)n || b >= (uint64_t)n) return CTWS_EINVAL;
-        const uint64_t i = find(a), j = find(b);
-        if (i == j) continue;
-        if (rank[i] > rank[j]) {
-            parent[j] = i;
-        } else {
-            parent[i] = j;
-            if (rank[i] == rank[j]) ++rank[j];
-        }
-    }
-    for (int64_t i = 0; i < n; ++i) out[i] = find((uint64_t)i);
     return CTWS_OK;
 }
 

@@ -305,9 +305,6 @@ __global__ void k_bits_chunk_count(const uint64_t*, int64_t, uint32_t*);
 __global__ void k_scan_chunks(const uint32_t*, int64_t, uint64_t*);
 __global__ void k_bits_compact(const uint64_t*, int64_t, const uint64_t*, uint64_t, uint64_t, uint64_t*);
 __global__ void k_u64_lookup(uint64_t*, int64_t, const uint64_t*, const uint64_t*, int64_t, unsigned long long*);
-hipError_t u64_sort(void* tmp, size_t& bytes, const uint64_t* in, uint64_t* out, int64_t n, hipStream_t stream);
-hipError_t u64_runs(void* tmp, size_t& bytes, const uint64_t* sorted, uint64_t* uniq, uint64_t* counts,
-                    uint64_t* n_runs, int64_t n, hipStream_t stream);
 // k_rag.hip (GraphWorkflow: face-adjacent id pairs of a block, sorted unique pairs with summed weights)
 struct RagArgs {
     const uint64_t* lab;        // the block's labels, (nz, ny, nx)
@@ -325,10 +322,6 @@ __global__ void k_rag_pairs(RagArgs);
 __global__ void k_pair_keys(const uint64_t*, int64_t, const uint64_t*, int64_t, int, uint64_t*, unsigned long long*);
 __global__ void k_pair_ones(uint64_t*, int64_t);
 __global__ void k_pair_unpack(const uint64_t*, int64_t, const uint64_t*, int, uint64_t*);
-hipError_t pair_sort(void* tmp, size_t& bytes, const uint64_t* keys_in, uint64_t* keys_out, const uint64_t* w_in,
-                     uint64_t* w_out, int64_t n, int end_bit, hipStream_t stream);
-hipError_t pair_reduce(void* tmp, size_t& bytes, const uint64_t* keys, uint64_t* uniq, const uint64_t* w,
-                       uint64_t* sums, uint64_t* n_runs, int64_t n, hipStream_t stream);
 // k_overlaps.hip (NodeLabelWorkflow: the (node, label) pairs of two label arrays, as weighted run heads)
 struct OvArgs {
     const uint64_t* nodes;      // the fragments, n voxels
@@ -387,8 +380,6 @@ constexpr int kRegfeatChunk = kMorphChunk;
 __global__ void k_regfeat_chunks(const uint64_t*, const uint64_t*, const double*, uint32_t, uint64_t*, double*);
 __global__ void k_regfeat_rows(const uint64_t*, const uint64_t*, const double*, uint32_t, const uint64_t*,
                                const uint64_t*, uint32_t, const uint64_t*, const double*, double*);
-hipError_t u32_exclusive_sum(void* tmp, size_t& bytes, const uint32_t* in, uint32_t* out, int64_t n,
-                             hipStream_t stream);
 // k_regcenter.hip (RegionCentersWorkflow: per object the first voxel of its box with the largest
 // exact squared distance to the box's background)
 constexpr uint32_t kRcInf = 0xFFFFFFFFu;  // a line without background (every finite value is below 2^31)
@@ -456,8 +447,6 @@ __global__ void k_ef_edge_keys(const uint64_t*, int64_t, const uint64_t*, int64_
 template <class T>
 __global__ void k_ef_samples(EfArgs);
 __global__ void k_ef_stats(const uint64_t*, uint32_t, uint32_t, double*);
-hipError_t ef_sort(void* tmp, size_t& bytes, const uint64_t* keys_in, uint64_t* keys_out, int64_t n, int end_bit,
-                   hipStream_t stream);
 // k_lifted.hip (LiftedFeaturesFromNodeLabelsWorkflow: the sparse lifted neighbourhood of a graph)
 constexpr int kLfWaves = 4;          // waves (= sources in flight) per workgroup of k_lf_bfs
 constexpr int kLfHashBits = 11;
@@ -493,9 +482,6 @@ __global__ void k_lf_fill(const uint64_t*, uint32_t, const uint32_t*, uint32_t*,
 __global__ void k_lf_sources(const uint64_t*, uint32_t, uint64_t, uint32_t*, unsigned long long*);
 __global__ void k_lf_bfs(LfArgs);
 __global__ void k_lf_unpack(const uint64_t*, int64_t, int, uint64_t*);
-hipError_t lf_scan(void* tmp, size_t& bytes, const uint32_t* in, uint32_t* out, int64_t n, hipStream_t stream);
-hipError_t lf_sort(void* tmp, size_t& bytes, const uint64_t* keys_in, uint64_t* keys_out, int64_t n, int end_bit,
-                   hipStream_t stream);
 // k_graphpost.hip (ConnectedComponentsWorkflow, SizeFilterAndGraphWatershedWorkflow: graph components
 // and the seeded graph watershed over an edge table)
 constexpr int kGpMaxIters = 34;  // rounds of a watershed, and pointer-jumping passes of a round: then an error
@@ -516,9 +502,20 @@ __global__ void k_gp_ws_write(const uint32_t*, const uint64_t*, uint64_t, uint64
 __global__ void k_gp_rl_keys(const uint64_t*, uint64_t, uint64_t*, uint32_t*, uint32_t*);
 __global__ void k_gp_rl_heads(const uint64_t*, const uint32_t*, uint64_t, uint32_t*);
 __global__ void k_gp_rl_write(const uint64_t*, const uint32_t*, const uint32_t*, uint64_t, uint64_t*);
-hipError_t gp_scan(void* tmp, size_t& bytes, const uint32_t* in, uint32_t* out, int64_t n, hipStream_t stream);
-hipError_t gp_sort(void* tmp, size_t& bytes, const uint64_t* keys_in, uint64_t* keys_out, const uint32_t* vals_in,
-                   uint32_t* vals_out, int64_t n, hipStream_t stream);
+
+// k_prims.hip (the device-wide primitives of the feature calls; tmp == nullptr: only size bytes)
+hipError_t sort_keys_u64(void* tmp, size_t& bytes, const uint64_t* keys_in, uint64_t* keys_out, int64_t n,
+                         int end_bit, hipStream_t stream);
+hipError_t sort_pairs_u64(void* tmp, size_t& bytes, const uint64_t* keys_in, uint64_t* keys_out,
+                          const uint64_t* vals_in, uint64_t* vals_out, int64_t n, int end_bit, hipStream_t stream);
+hipError_t sort_pairs_u64_u32(void* tmp, size_t& bytes, const uint64_t* keys_in, uint64_t* keys_out,
+                              const uint32_t* vals_in, uint32_t* vals_out, int64_t n, hipStream_t stream);
+hipError_t exclusive_sum_u32(void* tmp, size_t& bytes, const uint32_t* in, uint32_t* out, int64_t n,
+                             hipStream_t stream);
+hipError_t runs_u64(void* tmp, size_t& bytes, const uint64_t* sorted, uint64_t* uniq, uint64_t* counts,
+                    uint64_t* n_runs, int64_t n, hipStream_t stream);
+hipError_t reduce_by_key_sum_u64(void* tmp, size_t& bytes, const uint64_t* keys, uint64_t* uniq,
+                                 const uint64_t* vals, uint64_t* sums, uint64_t* n_runs, int64_t n, hipStream_t stream);
 
 // k_threshcc.hip (ThresholdedComponents: BlockComponents)
 struct TcParams {

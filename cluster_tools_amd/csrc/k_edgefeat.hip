@@ -21,7 +21,7 @@
 //                   edge << 32 | ordered(value), staged per wave in LDS and appended with one
 //                   atomicAdd per full stage; past the capacity the counter keeps counting and
 //                   nothing is written (the protocol of k_rag_pairs).
-//   ef_sort         radix sort of the keys over the bits [0, 32 + bits(n_edges)) (hipcub): the
+//   sort_keys_u64   radix sort of the keys over the bits [0, 32 + bits(n_edges)) (k_prims.hip): the
 //                   samples of an edge become one ascending segment.  The append order does not
 //                   matter: equal keys are equal samples.
 //   k_ef_stats      one wave per edge: the segment by two searches, per-lane double partial sums
@@ -29,8 +29,6 @@
 //                   alone), a second sweep for the variance, the quantiles by direct indexing.
 // Index arithmetic inside a block is 32-bit.  No float atomics anywhere: the results are
 // bit-reproducible.
-#include <hipcub/hipcub.hpp>
-
 #include "ctws_kernels.h"
 
 #pragma clang fp contract(off)
@@ -234,12 +232,6 @@ __global__ void __launch_bounds__(256) k_ef_stats(const uint64_t* __restrict__ k
         val = lane == 0 ? mean : lane == 1 ? var : lane == 9 ? (double)(m >> 1) : qv;
     }
     if (lane < 10u) out[(size_t)e * 10u + lane] = val;
-}
-
-// With tmp == nullptr the temporary storage is only sized.
-hipError_t ef_sort(void* tmp, size_t& bytes, const uint64_t* keys_in, uint64_t* keys_out, int64_t n, int end_bit,
-                   hipStream_t stream) {
-    return hipcub::DeviceRadixSort::SortKeys(tmp, bytes, keys_in, keys_out, (int)n, 0, end_bit, stream);
 }
 
 }  // namespace ctws

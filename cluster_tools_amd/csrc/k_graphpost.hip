@@ -47,8 +47,6 @@
 //   nodes, a scan numbers them, and k_gp_rl_write finds its run's head by a binary search.
 // Integer arithmetic and integer atomics only; the results do not depend on the atomics' order.
 // Node ids and ranks are 32-bit (n < 2^32, m < 2^32); loop counters are 64-bit.
-#include <hipcub/hipcub.hpp>
-
 #include "ctws_kernels.h"
 
 namespace ctws {
@@ -232,15 +230,6 @@ __global__ void __launch_bounds__(256) k_gp_rl_write(const uint64_t* __restrict_
         }
         out[sidx[p]] = v;
     }
-}
-
-// With tmp == nullptr the temporary storage is only sized.  The sort is stable.
-hipError_t gp_scan(void* tmp, size_t& bytes, const uint32_t* in, uint32_t* out, int64_t n, hipStream_t stream) {
-    return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, in, out, (size_t)n, stream);
-}
-hipError_t gp_sort(void* tmp, size_t& bytes, const uint64_t* keys_in, uint64_t* keys_out, const uint32_t* vals_in,
-                   uint32_t* vals_out, int64_t n, hipStream_t stream) {
-    return hipcub::DeviceRadixSort::SortPairs(tmp, bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0, 64, stream);
 }
 
 }  // namespace ctws

@@ -31,11 +31,9 @@
 //                  appended with ONE atomicAdd (the protocol of k_rag_pairs: the counter keeps
 //                  counting past the capacity and nothing is written there).  Every loop is
 //                  bounded by the depth, the probe limit, a list's length or the node count.
-//   lf_sort / k_lf_unpack  radix sort of the keys over their 2 b bits, key -> (u, v) rows.
+//   sort_keys_u64 (k_prims.hip) / k_lf_unpack  radix sort of the keys over their 2 b bits, key -> (u, v) rows.
 // Integer arithmetic only; node ids and adjacency offsets are 32-bit (n < 2^32, 2 m < 2^32), the
 // emit counter is 64-bit.
-#include <hipcub/hipcub.hpp>
-
 #include "ctws_kernels.h"
 
 namespace ctws {
@@ -255,15 +253,6 @@ __global__ void __launch_bounds__(256) k_lf_unpack(const uint64_t* __restrict__ 
         const uint64_t k = keys[i];
         ((ulonglong2*)out)[i] = make_ulonglong2(k >> b, k & mask);
     }
-}
-
-// With tmp == nullptr the temporary storage is only sized.
-hipError_t lf_scan(void* tmp, size_t& bytes, const uint32_t* in, uint32_t* out, int64_t n, hipStream_t stream) {
-    return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, in, out, (size_t)n, stream);
-}
-hipError_t lf_sort(void* tmp, size_t& bytes, const uint64_t* keys_in, uint64_t* keys_out, int64_t n, int end_bit,
-                   hipStream_t stream) {
-    return hipcub::DeviceRadixSort::SortKeys(tmp, bytes, keys_in, keys_out, (size_t)n, 0, end_bit, stream);
 }
 
 }  // namespace ctws

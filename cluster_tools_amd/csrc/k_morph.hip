@@ -16,8 +16,8 @@
 //                 stage, as in k_rag_pairs; the counter keeps counting past the capacity and
 //                 nothing is written there, so the host re-runs with the counted size.
 //                 The same pass takes the largest id (one atomicMax per wave).
-//   the sort      pair_sort (k_rag.hip) with the ids as keys over the bits of the largest id,
-//                 u64_runs (k_relabel.hip) on the sorted ids: the id table and each id's record
+//   the sort      sort_pairs_u64 (k_prims.hip) with the ids as keys over the bits of the largest id,
+//                 runs_u64 (k_prims.hip) on the sorted ids: the id table and each id's record
 //                 count.
 //   k_morph_rows  one wave per id: its lanes stride over the id's records and accumulate ten
 //                 integers (n, three coordinate sums in uint64, three minima, three maxima), a

@@ -26,13 +26,11 @@
 //                 np.unique of the block, and the labels are not read a second time.
 //   k_pair_keys   (u, v) -> rank(u) << b | rank(v): binary searches in a sorted table of the
 //                 endpoint values (the block's node table), b bits per rank.
-//   pair_sort / pair_reduce  radix sort of (key, weight) over the 2 b key bits and the sum of
-//                 the weights of equal keys (hipcub, device-wide).
+//   sort_pairs_u64 / reduce_by_key_sum_u64  radix sort of (key, weight) over the 2 b key bits
+//                 and the sum of the weights of equal keys (k_prims.hip, device-wide).
 //   k_pair_unpack key -> (table[key >> b], table[key & mask]).
 // Index arithmetic inside a block is 32-bit (a block holds fewer than 2^31 voxels) and there is
 // no division per voxel: one 32-bit division per row, on a wave-uniform value.
-#include <hipcub/hipcub.hpp>
-
 #include "ctws_kernels.h"
 
 namespace ctws {
@@ -185,16 +183,6 @@ __global__ void __launch_bounds__(256) k_pair_unpack(const uint64_t* __restrict_
         const uint64_t k = keys[i];
         ((ulonglong2*)out)[i] = make_ulonglong2(tab[k >> b], tab[k & mask]);
     }
-}
-
-// With tmp == nullptr the temporary storage is only sized.
-hipError_t pair_sort(void* tmp, size_t& bytes, const uint64_t* keys_in, uint64_t* keys_out, const uint64_t* w_in,
-                     uint64_t* w_out, int64_t n, int end_bit, hipStream_t stream) {
-    return hipcub::DeviceRadixSort::SortPairs(tmp, bytes, keys_in, keys_out, w_in, w_out, (int)n, 0, end_bit, stream);
-}
-hipError_t pair_reduce(void* tmp, size_t& bytes, const uint64_t* keys, uint64_t* uniq, const uint64_t* w,
-                       uint64_t* sums, uint64_t* n_runs, int64_t n, hipStream_t stream) {
-    return hipcub::DeviceReduce::ReduceByKey(tmp, bytes, keys, uniq, w, sums, n_runs, hipcub::Sum(), (int)n, stream);
 }
 
 }  // namespace ctws

@@ -12,7 +12,7 @@
 //   k_regfeat_count  labels only, 8 B per voxel.  A wave owns a (z, y) row, walks it in words of 64
 //                    voxels and writes the row's number of run heads (a head: the word's first
 //                    lane, or a lane whose predecessor holds another id).  An exclusive scan over
-//                    the rows (hipcub) gives each row's first record and the total, which sizes the
+//                    the rows (k_prims.hip) gives each row's first record and the total, which sizes the
 //                    record arrays exactly.
 //   k_regfeat_runs   labels and values, coalesced.  The run sums come from a segmented inclusive
 //                    scan over the word in float64: six shuffle steps, a lane adds only what lies
@@ -21,8 +21,8 @@
 //                    (the sort's key), (run length << 32 | record index) (the sort's value) and the
 //                    float64 sum at the record index.  Runs of the ignore label get length 0 and
 //                    sum 0.  The same pass takes the largest id (one integer atomicMax per wave).
-//   the sort         pair_sort (k_rag.hip; hipcub's LSD radix sort is stable, so an id's records
-//                    stay in scan order) over the bits of the largest id, u64_runs on the sorted
+//   the sort         sort_pairs_u64 (k_prims.hip; the LSD radix sort is stable, so an id's records
+//                    stay in scan order) over the bits of the largest id, runs_u64 on the sorted
 //                    ids: the id table and each id's record count.
 //   k_regfeat_chunks a wave per whole aligned chunk of kRegfeatChunk sorted records that holds one
 //                    id only: its (n, sum) into the chunk table.
@@ -32,8 +32,6 @@
 //                    butterfly finishes both and lanes 0..2 store [id, n, n ? sum / n : 0].  What a
 //                    lane adds, and in which order, follows from the sorted positions alone.
 // Index arithmetic inside a block is 32-bit (a block holds fewer than 2^31 voxels).
-#include <hipcub/hipcub.hpp>
-
 #include "ctws_kernels.h"
 
 namespace ctws {
@@ -235,12 +233,6 @@ __global__ void __launch_bounds__(256) k_regfeat_rows(const uint64_t* __restrict
             out[(size_t)w * 3u + lane] = lane == 0 ? (double)id : lane == 1 ? dn : (rn ? rs / dn : 0.0);
         }
     }
-}
-
-// With tmp == nullptr the temporary storage is only sized.
-hipError_t u32_exclusive_sum(void* tmp, size_t& bytes, const uint32_t* in, uint32_t* out, int64_t n,
-                             hipStream_t stream) {
-    return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, in, out, (int)n, stream);
 }
 
 }  // namespace ctws

@@ -43,78 +43,9 @@ def lib():
             if L.ctws_abi_version() != ABI_VERSION:
                 raise OSError("libctws.so ABI version %d, expected %d (include/ctws.h): rebuild it"
                               % (L.ctws_abi_version(), ABI_VERSION))
-            L.ctws_open.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-            L.ctws_close.argtypes = [C.c_void_p]
-            L.ctws_close.restype = None
-            L.ctws_last_error.argtypes = [C.c_void_p]
-            L.ctws_last_error.restype = C.c_char_p
-            for fn in ('ctws_ws_blocks', 'ctws_ws_blocks_device', 'ctws_ws_from_seeds', 'ctws_ws_from_seeds_device',
-                    'ctws_eval_begin', 'ctws_eval_add', 'ctws_eval_end', 'ctws_threshold_components',
-                    'ctws_threshold_components_ex', 'ctws_ufd_find'):
-                getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-            L.ctws_last_timings.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-            L.ctws_unique_u64.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64,
-                                          C.POINTER(C.c_int64)]
-            L.ctws_unique_counts_u64.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p,
-                                                 C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
-            L.ctws_lookup_u64.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
-                                          C.c_int64, C.POINTER(C.c_int64)]
-            L.ctws_set_table_u64.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
-            L.ctws_ufd_find.argtypes = [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
-            L.ctws_set_discard_u64.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
-            L.ctws_size_filter_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
-            L.ctws_size_filter_blocks_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
-            L.ctws_unique_pairs_u64.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p,
-                                                C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
-            for fn in ('ctws_rag_block', 'ctws_rag_block_device'):
-                getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int,
-                                           C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_void_p, C.c_void_p,
-                                           C.c_int64, C.POINTER(C.c_int64)]
-            for fn in ('ctws_label_overlaps', 'ctws_label_overlaps_device'):
-                getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_uint64,
-                                           C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
-            for fn in ('ctws_block_morphology', 'ctws_block_morphology_device'):
-                getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
-                                           C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
-            for fn in ('ctws_region_features_block', 'ctws_region_features_block_device'):
-                getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64,
-                                           C.c_int64, C.c_int, C.c_uint64, C.c_void_p, C.c_int64,
-                                           C.POINTER(C.c_int64)]
-            for fn in ('ctws_downscale_block', 'ctws_downscale_block_device'):
-                getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64,
-                                           C.POINTER(C.c_int64), C.c_int, C.c_void_p, C.c_int64, C.c_int64,
-                                           C.c_int64, C.POINTER(C.c_int)]
-            L.ctws_filter_taps.argtypes = [C.c_double, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
-            for fn in ('ctws_image_filter', 'ctws_image_filter_device'):
-                getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64,
-                                           C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_void_p]
-            for fn in ('ctws_region_centers', 'ctws_region_centers_device'):
-                getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_void_p]
-            for fn in ('ctws_edge_features_block', 'ctws_edge_features_block_device'):
-                getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_int64] * 6 + [
-                    C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]
-            for fn in ('ctws_lifted_neighborhood', 'ctws_lifted_neighborhood_device'):
-                getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int,
-                                           C.c_uint64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
-            L.ctws_lifted_limits.argtypes = [C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-            for fn in ('ctws_graph_components', 'ctws_graph_components_device'):
-                getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
-            for fn in ('ctws_graph_watershed', 'ctws_graph_watershed_device'):
-                getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
-                                           C.c_int, C.c_void_p]
-            L.ctws_threshold_components.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
-                                                    C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int, C.c_void_p,
-                                                    C.POINTER(C.c_int64)]
-            L.ctws_threshold_components_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
-                                                       C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_int,
-                                                       C.c_double, C.c_void_p, C.POINTER(C.c_int64)]
-            L.ctws_eval_begin.argtypes = [C.c_void_p, C.c_int64, C.c_int64]
-            L.ctws_eval_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int]
-            L.ctws_eval_end.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
-            L.ctws_debug_set_stop.argtypes = [C.c_void_p, C.c_int]
-            L.ctws_debug_read.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_int64]
-            L.ctws_debug_sqrt_int.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+            for name, (argtypes, restype) in SIGNATURES.items():
+                fn = getattr(L, name)
+                fn.argtypes, fn.restype = argtypes, restype
             _lib = L
         return _lib
 
@@ -122,19 +53,76 @@ def lib():
 # include/ctws.h CTWS_ABI_VERSION (2: the library's own RCCL communicator entry points removed)
 ABI_VERSION = 2
 
-EXPORTED_SYMBOLS = ('ctws_abi_version', 'ctws_open', 'ctws_close', 'ctws_last_error', 'ctws_ws_blocks',
-                    'ctws_ws_blocks_device', 'ctws_last_timings', 'ctws_unique_u64', 'ctws_unique_counts_u64', 'ctws_set_table_u64', 'ctws_lookup_u64',
-                    'ctws_debug_set_stop', 'ctws_debug_read', 'ctws_debug_sqrt_int', 'ctws_ws_from_seeds', 'ctws_ws_from_seeds_device',
-                    'ctws_eval_begin', 'ctws_eval_add', 'ctws_eval_end', 'ctws_threshold_components',
-                    'ctws_threshold_components_ex', 'ctws_ufd_find', 'ctws_set_discard_u64', 'ctws_size_filter_blocks',
-                    'ctws_size_filter_blocks_device', 'ctws_unique_pairs_u64', 'ctws_rag_block', 'ctws_rag_block_device',
-                    'ctws_edge_features_block', 'ctws_edge_features_block_device', 'ctws_label_overlaps',
-                    'ctws_label_overlaps_device', 'ctws_block_morphology', 'ctws_block_morphology_device',
-                    'ctws_region_features_block', 'ctws_region_features_block_device', 'ctws_downscale_block',
-                    'ctws_downscale_block_device', 'ctws_region_centers', 'ctws_region_centers_device',
-                    'ctws_filter_taps', 'ctws_image_filter', 'ctws_image_filter_device', 'ctws_lifted_neighborhood',
-                    'ctws_lifted_neighborhood_device', 'ctws_lifted_limits', 'ctws_graph_components',
-                    'ctws_graph_components_device', 'ctws_graph_watershed', 'ctws_graph_watershed_device')
+_p, _i, _i64, _u64, _f64 = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_double
+_pi, _pi64 = C.POINTER(C.c_int), C.POINTER(C.c_int64)
+_BLOCKS = ((_p, _p, _p, _i), _i)  # handle, cfg, blocks, n_blocks
+_RAG = ((_p, _p, _i64, _i64, _i64, _i, _p, _i64, _pi64, _p, _p, _i64, _pi64), _i)
+_OVERLAPS = ((_p, _p, _p, _i64, _i, _u64, _p, _i64, _pi64), _i)
+_MORPHOLOGY = ((_p, _p, _i64, _i64, _i64, _pi64, _p, _i64, _pi64), _i)
+_REGION_FEATURES = ((_p, _p, _p, _i, _i64, _i64, _i64, _i, _u64, _p, _i64, _pi64), _i)
+_DOWNSCALE = ((_p, _p, _i, _i64, _i64, _i64, _pi64, _i, _p, _i64, _i64, _i64, _pi), _i)
+_IMAGE_FILTER = ((_p, _p, _i, _i64, _i64, _i64, _i, C.POINTER(_f64), _i, _i, _p), _i)
+_REGION_CENTERS = ((_p, _p, _i64, _i64, _p, _p, _p, _p, C.POINTER(_f64), _p, _p), _i)
+_EDGE_FEATURES = ((_p, _p, _p, _i) + (_i64,) * 6 + (_i, _p, _i64, _p, _i64, _p, _pi64), _i)
+_LIFTED = ((_p, _p, _i64, _p, _i64, _i, _i, _u64, _p, _i64, _pi64), _i)
+_GRAPH_COMPONENTS = ((_p, _p, _i64, _p, _i64, _p), _i)
+_GRAPH_WATERSHED = ((_p, _p, _p, _i64, _p, _i64, _i, _p), _i)
+
+# Every function of include/ctws.h: name -> (argtypes, restype).  lib() sets both from this table,
+# and its names are the library's exported symbols (tests/test_abi.py holds them against the header).
+SIGNATURES = {
+    'ctws_abi_version': ([], _i),
+    'ctws_open': ([_i, C.POINTER(_p)], _i),
+    'ctws_close': ([_p], None),
+    'ctws_last_error': ([_p], C.c_char_p),
+    'ctws_last_timings': ([_p, _p, _p, _i], _i),
+    'ctws_ws_blocks': _BLOCKS,
+    'ctws_ws_blocks_device': _BLOCKS,
+    'ctws_ws_from_seeds': _BLOCKS,
+    'ctws_ws_from_seeds_device': _BLOCKS,
+    'ctws_unique_u64': ([_p, _p, _i64, _i, _p, _i64, _pi64], _i),
+    'ctws_unique_counts_u64': ([_p, _p, _i64, _i, _p, _p, _i64, _pi64], _i),
+    'ctws_set_table_u64': ([_p, _p, _p, _i64], _i),
+    'ctws_lookup_u64': ([_p, _p, _i64, _i, _p, _p, _i64, _pi64], _i),
+    'ctws_ufd_find': ([_i64, _p, _i64, _p], _i),
+    'ctws_set_discard_u64': ([_p, _p, _i64], _i),
+    'ctws_size_filter_blocks': ([_p, _p, _i, _i], _i),
+    'ctws_size_filter_blocks_device': ([_p, _p, _i, _i], _i),
+    'ctws_unique_pairs_u64': ([_p, _p, _p, _i64, _i, _p, _p, _i64, _pi64], _i),
+    'ctws_rag_block': _RAG,
+    'ctws_rag_block_device': _RAG,
+    'ctws_label_overlaps': _OVERLAPS,
+    'ctws_label_overlaps_device': _OVERLAPS,
+    'ctws_block_morphology': _MORPHOLOGY,
+    'ctws_block_morphology_device': _MORPHOLOGY,
+    'ctws_region_features_block': _REGION_FEATURES,
+    'ctws_region_features_block_device': _REGION_FEATURES,
+    'ctws_downscale_block': _DOWNSCALE,
+    'ctws_downscale_block_device': _DOWNSCALE,
+    'ctws_filter_taps': ([_f64, _i, _p, _pi], _i),
+    'ctws_image_filter': _IMAGE_FILTER,
+    'ctws_image_filter_device': _IMAGE_FILTER,
+    'ctws_region_centers': _REGION_CENTERS,
+    'ctws_region_centers_device': _REGION_CENTERS,
+    'ctws_edge_features_block': _EDGE_FEATURES,
+    'ctws_edge_features_block_device': _EDGE_FEATURES,
+    'ctws_lifted_neighborhood': _LIFTED,
+    'ctws_lifted_neighborhood_device': _LIFTED,
+    'ctws_lifted_limits': ([_i64, _pi64, _pi64], _i),
+    'ctws_graph_components': _GRAPH_COMPONENTS,
+    'ctws_graph_components_device': _GRAPH_COMPONENTS,
+    'ctws_graph_watershed': _GRAPH_WATERSHED,
+    'ctws_graph_watershed_device': _GRAPH_WATERSHED,
+    'ctws_threshold_components': ([_p, _p, _p, _i64, _i64, _i64, _i, _i, _f64, _i, _p, _pi64], _i),
+    'ctws_threshold_components_ex': ([_p, _p, _i, _p, _i64, _i64, _i64, _i, _i, _f64, _i, _f64, _p, _pi64], _i),
+    'ctws_eval_begin': ([_p, _i64, _i64], _i),
+    'ctws_eval_add': ([_p, _p, _p, _i64, _i, _i], _i),
+    'ctws_eval_end': ([_p, _p, _pi64], _i),
+    'ctws_debug_set_stop': ([_p, _i], _i),
+    'ctws_debug_read': ([_p, C.c_char_p, _i, _p, _i64], _i),
+    'ctws_debug_sqrt_int': ([_p, C.c_uint32, C.c_uint32, _p], _i),
+}
+EXPORTED_SYMBOLS = tuple(SIGNATURES)
 
 
 def ufd_find(n_labels, pairs):
